@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot-path benchmark (BASELINE.json metric: GTEPS of mxv on R-MAT scale-24).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--workload NAME] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the resident graph: the masked SSSP relaxation
     w<~visited.S> = min(w, A min.+ u)          (GrB_mxv, GrB_MIN_PLUS_SEMIRING_FP32, accum GrB_MIN_FP32)
@@ -10,9 +10,12 @@ on the R-MAT scale-24 graph (north-star target line), inputs already resident in
 and every step ends with an RCCL all-gather of the w slices into the next u (strong scaling).
 
 Prints ONE JSON line on rank 0 (see the driver contract); `roofline` is computed from the algorithmic
-bytes of DESIGN.md / SURVEY.md section 8d and the HIP-event duration of the timed region; `cpu_baseline`
-times the C oracle (OpenMP, all host cores) on the same workload -- it is the checker doubling as the
-reported CPU baseline, never the product.
+bytes of DESIGN.md / SURVEY.md section 8d and the HIP-event duration of the timed region.  A plain run
+sets up, warms up, times --steps steps and prints the line (`ms_per_step`: wall time of one timed step);
+--dump-outputs DIR also writes the last step's output as .npy files.  --full adds everything else: the
+check of the timed output (`verified`), the lines under `extra`, the warm layout build, the library's
+build state and `cpu_baseline`, which times the C oracle (OpenMP, all host cores) on the same workload --
+it is the checker doubling as the reported CPU baseline, never the product.
 """
 import argparse
 import ctypes
@@ -28,6 +31,8 @@ if ROOT not in sys.path:
 
 PROFILE_ROUND = 5  # PMC traffic profiles of kernels from earlier rounds do not describe this library: only profiles/r05 (and later) count
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md); 6290 GB/s measured copy
+DUMP_MAX_ENTRIES = 1 << 21  # --dump-outputs: entries per array (3 arrays of at most 8 + 8 + 16 MB)
+DUMP_SEED = 20240607
 
 
 def measured_traffic(workload, scale):
@@ -89,7 +94,7 @@ def parse():
                         "counts (sharded.shard_setup); the blocks then run the natural-order layouts of rounds 1-5")
     p.add_argument("--streamed", action="store_true", help="mxm: run the unmasked product in row batches with the output streamed")
     p.add_argument("--stream-budget-gb", type=float, default=64.0, help="mxm --streamed: device bytes one batch's product may take")
-    p.add_argument("--extra", action="store_true", help="(kept for old command lines: the secondary workloads now run by default)")
+    p.add_argument("--extra", action="store_true", help="(kept for old command lines: the secondary workloads run with --full)")
     p.add_argument("--no-extra", action="store_true", help="headline workload only: skip the lines reported under 'extra'")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="N > 1: torch.distributed backend (nccl = RCCL; gloo only to rehearse the N-rank code path on a box with fewer GPUs)")
@@ -102,7 +107,21 @@ def parse():
                         "proves on a single-GPU box that RCCL accepts the library's buffers; the numbers are no multi-GPU measurement")
     p.add_argument("--overlap-chunks", type=int, default=2,
                    help="N > 1: row blocks per rank; the all-gather of block c overlaps the product of block c + 1 (1 = no overlap)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything besides the headline timing: the check of the timed output (`verified`), the CPU baselines, the lines "
+                        "under `extra`, the warm layout build and the library's build state; without it a run sets up, warms up, times "
+                        "--steps steps and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy (float32 / float64; a fixed, seeded "
+                        "sample of at most %d entries of a larger vector)" % DUMP_MAX_ENTRIES)
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and not (args.workload.startswith("mxv_") or args.workload == "kron26"):
+        p.error(f"--dump-outputs is implemented for the mxv workloads, not for {args.workload}")
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra = args.no_warm_build = True
+    return args
 
 
 def algorithmic_bytes_mxv(nnz_active, m, n, v_a, v_u, v_w, accum, mask):
@@ -391,6 +410,34 @@ class MxvWorkload:
     def bytes_per_step(self):
         return algorithmic_bytes_mxv(self.nnz_active_local, self.m, self.n, self.v_a, self.v_u, self.v_w,
                                      accum=self.accum is not None, mask=True)
+
+    def dump_outputs(self, dirname):
+        """--dump-outputs: the vector a caller of the timed path holds after the last step -- w (one block), or with N ranks the
+        replica of u the exchange filled for the next step -- as w_index / w_present / w_values (.npy; a seeded sample of
+        DUMP_MAX_ENTRIES indices when the vector is longer, the same indices in every run of the same size) and w_summary
+        (length, stored entries, sum of the stored values over the whole vector)."""
+        import numpy as np
+
+        from graphblas_amd import device
+
+        vec = self.ov.current_u() if self.ov is not None else self.w
+        vals, words = device.vector_device_views(vec, pin=False)
+        n = vals.numel()
+        has = self._bits(words, n)
+        vals = vals.to(self.torch.float64)
+        summary = np.array([n, int(has.sum().item()), float(vals[has].sum().item())], dtype=np.float64)
+        if n > DUMP_MAX_ENTRIES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ENTRIES, replace=False))
+        else:
+            idx = np.arange(n)
+        sel = self.torch.from_numpy(idx).to(vals.device)
+        present = has[sel].cpu().numpy()
+        values = np.where(present, vals[sel].cpu().numpy(), 0.0)
+        os.makedirs(dirname, exist_ok=True)
+        np.save(os.path.join(dirname, "w_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(dirname, "w_present.npy"), present.astype(np.float32))
+        np.save(os.path.join(dirname, "w_values.npy"), values.astype(np.float32))
+        np.save(os.path.join(dirname, "w_summary.npy"), summary)
 
 
 def probe_suitesparse():
@@ -1224,7 +1271,7 @@ def main():
         gc.collect()
         device.trim_memory()
 
-    def run(workload, scale, steps, warmup, weights="int255", fresh_outputs=False, ranked=None):
+    def run(workload, scale, steps, warmup, weights="int255", fresh_outputs=False, ranked=None, dump_dir=None):
         sr = {"mxv_min_plus_masked": "min_plus", "mxv_lor_land_masked": "lor_land", "mxv_min_plus": "min_plus"}[workload]
         visited = 0.0 if workload == "mxv_min_plus" else args.visited
         wl = MxvWorkload(gb, torch, scale, rank, world, sr, visited, block=block, chunks=max(1, args.overlap_chunks), force_dist=args.force_dist,
@@ -1271,7 +1318,9 @@ def main():
         kernel_ms = ev_ms / steps
         achieved = wl.bytes_per_step() / (kernel_ms * 1e-3) / 1e9
         stats = device.last_stats()
-        verified = wl.verify()
+        if dump_dir and rank == 0:
+            wl.dump_outputs(dump_dir)
+        verified = wl.verify() if args.full else None
         if scale >= 22 and workload == "mxv_min_plus_masked" and weights == "int255" and not fresh_outputs and not (args.ranked if ranked is None else ranked):
             warm_layout_build(sr, visited, scale)
         res = {
@@ -1338,7 +1387,7 @@ def main():
         return main_sssp(args, gb, torch, device, rank, world)
     if args.workload in ("mxm_plus_times", "mxm_plus_times_masked", "mxm_plus_times_cmask"):
         return main_mxm(args, gb, torch, device, rank, world, dist, barrier)
-    wl, res = run(args.workload, args.scale, args.steps, args.warmup)
+    wl, res = run(args.workload, args.scale, args.steps, args.warmup, dump_dir=args.dump_outputs)
     cpu = cpu_line(wl) if (rank == 0 and world == 1 and not args.no_cpu_baseline and not args.force_dist) else None
     # ---- the rest of the BASELINE metric, in the same line under `extra`: the BFS level step (configs[2]) and SpGEMM A (+.x) A
     #      at scale 20 (one GPU: the materialised product) and scale 22 (configs[3]; row batches on one GPU, row-sharded on N) ----
@@ -1428,7 +1477,6 @@ def main():
                                        f"row-shard x{world}" + (f", ranked labels, stripes of {args.stripe} rows dealt block-cyclically" if args.ranked else "") +
                                        (f" ({res['exchange']['chunks_per_rank']} row blocks per rank) + RCCL all-gather of the w slices into "
                                                                 "the other replica of u, overlapped with the next block's product" if "exchange" in res else ""))},
-            "verified": res["verified"],
             "shard_setup": ("the blocks were handed the global column counts (sharded.shard_setup / GrX_Matrix_shard_setup): the library ranked the "
                             "columns and laid the blocks out in that order" + ("; the replicas of u are RCCL buffers (pinned natural): the N-rank "
                             "products run the natural-order layouts all the same, compute-only block runs (--block) the ordered ones"
@@ -1441,8 +1489,10 @@ def main():
             "roofline": res["roofline"],
             "cpu_baseline": cpu,
             "stats": res["stats"],
-            "build": library_build_state(),
         }
+        if args.full:  # (a plain run neither checks the timed output nor the library's build state: --dump-outputs hands the output out)
+            out["verified"] = res["verified"]
+            out["build"] = library_build_state()
         if "exchange" in res:
             out["exchange"] = res["exchange"]
         if args.share_gpus or args.backend != "nccl" or (args.force_dist and world == 1):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC counters of the kernels of one bench workload:  gpu_pmc.sh TAG WORKLOAD "COUNTER COUNTER ..." [ENV=VAL ...]
 TAG=$1; WL=$2; CTRS=$3; shift 3; OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-env "$@" timeout 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d "$OUT/p" -o c -- python bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/b.json" 2> "$OUT/b.err"
+env "$@" timeout 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d "$OUT/p" -o c -- python bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/b.json" 2> "$OUT/b.err"
 echo "== $WL [$CTRS] $* rc=$?"
 python - "$OUT" <<'PY'
 import csv, sys, glob, os, collections

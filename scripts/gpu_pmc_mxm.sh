@@ -4,7 +4,7 @@ OUT=gpurun_out/pmc_mxm; mkdir -p "$OUT"; export TMPDIR=/tmp
 i=0
 for grp in "$@"; do
   i=$((i+1)); d="$OUT/g$i"
-  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$d" -o c -- python bench.py --workload mxm_plus_times --scale 20 --steps 1 --warmup 0 --no-cpu-baseline > "$d.json" 2> "$d.err"
+  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$d" -o c -- python bench.py --full --workload mxm_plus_times --scale 20 --steps 1 --warmup 0 --no-cpu-baseline > "$d.json" 2> "$d.err"
   echo "== [$grp] rc=$?"
   python - "$d" <<'PY'
 import csv, sys, glob, os, collections

@@ -7,7 +7,7 @@ OUT=gpurun_out/r06c; mkdir -p $OUT; export TMPDIR=/tmp
 python scripts/ref_shares.py --scale 24 > $OUT/ref_shares_s24.json 2> $OUT/ref_shares.err
 for v in default rt_fold rt_head10k rt_head40k rt_head160k rt_nogather; do
   if [ $v = default ]; then unset GRB_MI355X_LIB; else export GRB_MI355X_LIB=$PWD/build/variants/$v/libgrb_mi355x.so; fi
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$v -o b -- python bench.py --steps 10 --no-cpu-baseline --no-extra > $OUT/$v.json 2> $OUT/$v.err
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$v -o b -- python bench.py --full --steps 10 --no-cpu-baseline --no-extra > $OUT/$v.json 2> $OUT/$v.err
   echo "== $v $(python -c "import json; d=json.loads(open('$OUT/$v.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['verified'])")"
   python - $OUT/$v/b_kernel_stats.csv <<'PY'
 import csv, sys

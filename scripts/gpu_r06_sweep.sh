@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6: layout options of the headline re-swept on the round-6 library (the balance between the kernels moved since round 4)
 OUT=gpurun_out/r06f; mkdir -p $OUT
-one() { tag=$1; shift; env "$@" python bench.py --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'], 'build_ms', round(d['layout_build_call_ms'],1), 'cache_GB', round(d['preprocess_bytes']/1e9,2))"; }
+one() { tag=$1; shift; env "$@" python bench.py --full --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'], 'build_ms', round(d['layout_build_call_ms'],1), 'cache_GB', round(d['preprocess_bytes']/1e9,2))"; }
 one default A=1
 one hub128 GRB_HUB_MIN_LEN=128
 one hub256 GRB_HUB_MIN_LEN=256

@@ -4,8 +4,8 @@
 OUT=gpurun_out/r06i; mkdir -p $OUT; export TMPDIR=/tmp
 [ -n "$VARIANT" ] && export GRB_MI355X_LIB=$PWD/build/variants/$VARIANT/libgrb_mi355x.so
 python -m pytest tests/test_vertex_order.py -m gpu -x -q -k "sorted_row_tiles or ordered_product or shard_setup or ranked" 2>&1 | tail -3
-one() { tag=$1; shift; env "$@" python bench.py --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'], 'build_ms', round(d['layout_build_call_ms'],1), 'cache_GB', round(d['preprocess_bytes']/1e9,2), 'tails', d['stats'].get('long_tails'))"; }
-oneu() { tag=$1; shift; env "$@" python bench.py --workload mxv_min_plus --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'])"; }
+one() { tag=$1; shift; env "$@" python bench.py --full --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'], 'build_ms', round(d['layout_build_call_ms'],1), 'cache_GB', round(d['preprocess_bytes']/1e9,2), 'tails', d['stats'].get('long_tails'))"; }
+oneu() { tag=$1; shift; env "$@" python bench.py --full --workload mxv_min_plus --steps 30 --no-cpu-baseline --no-extra 2>$OUT/$tag.err | tee $OUT/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['ms_per_step'],4), 'verified', d['verified'])"; }
 one cold0 GRB_COLD_IN_ROWS=0
 one cold1024 GRB_COLD_IN_ROWS=1024
 one cold256 GRB_COLD_IN_ROWS=256
@@ -18,7 +18,7 @@ one cold0_b GRB_COLD_IN_ROWS=0
 oneu unmasked_cold0 GRB_COLD_IN_ROWS=0
 oneu unmasked_cold1024 GRB_COLD_IN_ROWS=1024
 for c in 0 1024; do
-  GRB_COLD_IN_ROWS=$c timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_cold$c -o b -- python bench.py --steps 10 --no-cpu-baseline --no-extra > /dev/null 2>&1
+  GRB_COLD_IN_ROWS=$c timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_cold$c -o b -- python bench.py --full --steps 10 --no-cpu-baseline --no-extra > /dev/null 2>&1
   echo "kernels, cold_in_rows=$c"
   python - $OUT/prof_cold$c/b_kernel_stats.csv <<'PY'
 import csv, sys

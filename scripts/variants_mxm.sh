@@ -25,7 +25,7 @@ run)
   export TMPDIR=/tmp
   O=gpurun_out/variants_mxm; mkdir -p $O
   one() {
-    timeout 600 python bench.py --workload mxm_plus_times --scale ${VARIANT_SCALE:-20} --steps 3 --warmup 1 --no-cpu-baseline --no-extra 2>/dev/null \
+    timeout 600 python bench.py --full --workload mxm_plus_times --scale ${VARIANT_SCALE:-20} --steps 3 --warmup 1 --no-cpu-baseline --no-extra 2>/dev/null \
       | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', round(d['ms_per_step'],2), 'verified', d['verified'])"
   }
   unset GRB_MI355X_LIB; one default
@@ -34,7 +34,7 @@ run)
     tag="$(basename "$(dirname "$lib")")"
     GRB_MI355X_LIB="$ROOT/$lib" one "$tag"
     if [ -n "$VARIANT_PROFILE" ]; then
-      (cd /tmp && GRB_MI355X_LIB="$ROOT/$lib" rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/prof_$tag -o p -- python $ROOT/bench.py --workload mxm_plus_times --scale ${VARIANT_SCALE:-20} --steps 2 --warmup 1 --no-cpu-baseline --no-extra > /dev/null 2>&1)
+      (cd /tmp && GRB_MI355X_LIB="$ROOT/$lib" rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/prof_$tag -o p -- python $ROOT/bench.py --full --workload mxm_plus_times --scale ${VARIANT_SCALE:-20} --steps 2 --warmup 1 --no-cpu-baseline --no-extra > /dev/null 2>&1)
       f=$(find $O/prof_$tag -name "*kernel_stats.csv" | head -1); grep "grb::k_spgemm" "$f" | head -6 | awk -F'","' '{printf "    %-70s calls %s avg_us %.0f\n", substr($1,2,70), $2, $4/1000}'
     fi
   done

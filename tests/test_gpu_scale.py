@@ -676,7 +676,7 @@ def test_rccl_one_rank_world():
     assert out["backend"] == "nccl" and out["ok"], out
     for args in (["--scale", "20", "--steps", "3", "--warmup", "3", "--no-extra", "--no-cpu-baseline"],
                  ["--workload", "mxm_plus_times", "--scale", "17", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--backend", "nccl"] + args, capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--force-dist", "--backend", "nccl"] + args, capture_output=True, text=True,
                            timeout=900, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         assert len(r.stdout.strip().splitlines()) == 1, r.stdout[-2000:]  # (bench.py keeps stdout to its one JSON line)
