@@ -422,7 +422,7 @@ def vec_assign_scalar(w: OVec, value, *, mask: OVec | None = None, mask_comp=Fal
     return OVec.from_dense(w_has, w_val, wt)
 
 
-_NP_BINOP = {"plus": np.add, "times": np.multiply, "min": np.minimum, "max": np.maximum, "minus": np.subtract,
+_NP_BINOP = {"plus": np.add, "times": np.multiply, "min": np.fmin, "max": np.fmax, "minus": np.subtract,
              "first": lambda a, b: a, "second": lambda a, b: b, "lor": np.logical_or, "land": np.logical_and, "lxor": np.logical_xor}
 
 
@@ -499,6 +499,17 @@ def vec_reduce(u: OVec, monoid: str):
         f = {"lor": np.logical_or, "plus": np.logical_or, "max": np.logical_or, "land": np.logical_and, "times": np.logical_and,
              "min": np.logical_and, "lxor": np.logical_xor, "lxnor": lambda a, b: ~np.logical_xor(a, b)}[monoid]
         return bool(f.reduce(v)) if hasattr(f, "reduce") else bool(__import__("functools").reduce(f, v))
+    if monoid not in ("plus", "times", "min", "max"):
+        raise NotImplementedError(monoid)
+    if v.dtype.kind == "f":
+        # a true left-to-right fold with no seed (the identity +0.0 would turn a sum of -0.0 into +0.0; numpy's add.reduce sums
+        # pairwise); min / max are fmin / fmax: a NaN operand is ignored (grb_oracle_typed.inc, ORA_MIN / ORA_MAX)
+        f = {"plus": np.add, "times": np.multiply, "min": np.fmin, "max": np.fmax}[monoid]
+        acc = v[0]
+        with np.errstate(all="ignore"):
+            for x in v[1:]:
+                acc = f(acc, x)
+        return acc.item()
     with np.errstate(over="ignore"):
         if monoid == "plus":
             return np.add.reduce(v, dtype=v.dtype).item()
@@ -506,9 +517,7 @@ def vec_reduce(u: OVec, monoid: str):
             return np.multiply.reduce(v, dtype=v.dtype).item()
         if monoid == "min":
             return v.min().item()
-        if monoid == "max":
-            return v.max().item()
-    raise NotImplementedError(monoid)
+        return v.max().item()
 
 
 def vec_ewise(u: OVec, v: OVec, binop: str, *, union: bool) -> OVec:
@@ -521,7 +530,7 @@ def vec_ewise(u: OVec, v: OVec, binop: str, *, union: bool) -> OVec:
     hu, du = u.dense(t)
     hv, dv = v.dense(t)
     hu, hv = hu.astype(bool), hv.astype(bool)
-    f = {"plus": np.add, "times": np.multiply, "min": np.minimum, "max": np.maximum, "minus": np.subtract,
+    f = {"plus": np.add, "times": np.multiply, "min": np.fmin, "max": np.fmax, "minus": np.subtract,
          "first": lambda a, b: a, "second": lambda a, b: b, "lor": np.logical_or, "land": np.logical_and,
          "lxor": np.logical_xor}[binop]
     with np.errstate(over="ignore"):

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spgemm_hash(const MxmArgs a, const
     const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
     for (int k = tid; k < TABLE; k += MM_BLOCK) {
         s_key[k] = -1;
-        if (NUMERIC) s_val[k] = monoid_identity<T, W>(monoid);
+        if (NUMERIC) s_val[k] = acc_seed<T, W>(monoid);
     }
     if (tid == 0) s_cnt = 0;
     __syncthreads();
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spgemm_spa(const MxmArgs a, const 
         // ordered sweep of the presence words: emit sorted (col, value), restore identity / zero
         const int64_t out0 = a.Tp[row];
         T *Tx = (T *)a.Tx;
-        const W ident = monoid_identity<T, W>(monoid);
+        const W ident = acc_seed<T, W>(monoid);
         for (int64_t w0 = 0; w0 < a.spa_words; w0 += MM_BLOCK) {
             const int64_t w = w0 + tid;
             unsigned long long b = (w < a.spa_words) ? bits[w] : 0ull;
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(MM_WIN_BLOCK) void k_spgemm_win(const MxmArgs a, co
     const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
     const int64_t row = rows[blockIdx.x];
     if (a.wrow && a.wrow[row] >= 0) return;  // (the row's windows are units of k_spgemm_unit)
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = acc_seed<T, W>(monoid);
     for (int k = tid; k < MM_WIN; k += MM_WIN_BLOCK) s_acc[k] = ident;
     if (tid < MM_WIN / 64) s_bits[tid] = 0ull;
     __syncthreads();
@@ -834,7 +834,7 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
     W *acc = s_acc[NUMERIC ? uib : 0];
     const int monoid = a.monoid, mult = a.mult;
     const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = acc_seed<T, W>(monoid);
     // (an iso operand stores one value: read once, not once per product)
     T a_iso_val = (T)0, b_iso_val = (T)0;
     if constexpr (NUMERIC) {
@@ -1310,7 +1310,7 @@ __global__ __launch_bounds__(MM_WIN_BLOCK) void k_spgemm_unit_dense(const MxmArg
     const int bslot = r.aux;  // (the symbolic pass kept the bitmap: no atomics on it here)
     const int monoid = a.monoid, mult = a.mult;
     const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = acc_seed<T, W>(monoid);
     unsigned long long csum_mine = 0;
     for (int k = tid; k < MM_WIN; k += MM_WIN_BLOCK) s_acc[k] = ident;
     if (tid < MM_WIN / 64) s_bits[tid] = bslot >= 0 ? a.bm_pool[(int64_t)bslot * (MM_WIN / 64) + tid] : 0ull;
@@ -1661,7 +1661,7 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spgemm_mhash(const MxmArgs a, cons
     const int64_t mlo = a.Mp[row], mhi = a.Mp[row + 1];
     for (int k = tid; k < TABLE; k += MM_BLOCK) {
         s_key[k] = -1;
-        s_val[k] = monoid_identity<T, W>(monoid);
+        s_val[k] = acc_seed<T, W>(monoid);
         s_hit[k] = 0;
     }
     __syncthreads();
@@ -1719,7 +1719,7 @@ __global__ __launch_bounds__(MM_WIN_BLOCK) void k_spgemm_mwin(const MxmArgs a, c
     const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
     const int64_t row = rows[blockIdx.x];
     if (a.wrow && a.wrow[row] >= 0) return;  // (the row's windows are units of k_spgemm_unit)
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = acc_seed<T, W>(monoid);
     for (int k = tid; k < MM_WIN; k += MM_WIN_BLOCK) s_acc[k] = ident;
     if (tid < MM_WIN / 64) { s_bits[tid] = 0ull; s_mbits[tid] = 0ull; }
     const int64_t mlo = a.Mp[row], mhi = a.Mp[row + 1];
@@ -2099,7 +2099,7 @@ static void run_bins(MxmArgs &a, const RowBins &rb)
         if (NUMERIC) {
             const int64_t nv = G * words * 64;
             hipLaunchKernelGGL((k_fill_ident<W>), dim3((unsigned)ceil_div(nv, 256)), dim3(256), 0, ctx().stream, vals.p, nv,
-                               monoid_identity<T, W>(a.monoid));
+                               acc_seed<T, W>(a.monoid));
         }
         a.spa_bits = bits.p;
         a.spa_vals = vals.p;

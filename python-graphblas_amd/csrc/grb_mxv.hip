@@ -1261,7 +1261,7 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
             }
         }
         hipLaunchKernelGGL((k_long_init<W>), dim3((unsigned)ceil_div(a.n_long, 256)), dim3(256), 0, ctx().stream, tl_val.p, tl_has.p,
-                           a.n_long, monoid_identity<T, W>(a.monoid), a.long_rows, a.m_bits, a.has_mask, a.m_comp, long_act.p,
+                           a.n_long, pull_seed<T, W>(a, a.monoid), a.long_rows, a.m_bits, a.has_mask, a.m_comp, long_act.p,
                            ((by_class || by_strip) && a.u_full) ? 1 : 0, (by_strip && acc_is_ordered<W>(a.monoid)) ? 1 : 0,
                            (hot_fast && a.has_mask) ? long_act8.p : nullptr, A->rt_state == 1 ? A->d_rt_counter : nullptr, pb);
         a.tl_ord = (by_strip && acc_is_ordered<W>(a.monoid)) ? 1 : 0;
@@ -2034,7 +2034,7 @@ static bool push_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bina
     GRB_DISPATCH_TYPE(st, T, {
         using W = typename Widen<T>::type;
         hipLaunchKernelGGL((k_fill_w<W>), dim3((unsigned)ceil_div(n_out, 256)), dim3(256), 0, ctx().stream, (W *)t_val.p, n_out,
-                           monoid_identity<T, W>(monoid));
+                           acc_seed<T, W>(monoid));
         if (work > 0) {
             const int64_t nthreads = ceil_div(work, PUSH_CHUNK);
             const int need_a = !(mult == OP_PAIR || mult == OP_FIRST || mult == OP_ANY);

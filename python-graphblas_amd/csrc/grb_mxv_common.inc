@@ -128,6 +128,13 @@ __global__ void k_tile_table(const int64_t *rowptr, int64_t m, int64_t nnz, int 
     tile_row[t] = lo;
 }
 
+// the starting value of a pull kernel's accumulator: acc_seed -- except under the absorbing fill (has_by_value), which only runs on
+// finite matrices with bounded operands (no NaN product can reach it) and detects a product as "the accumulator left the identity"
+template <typename T, typename W> GRB_HD W pull_seed(const PullArgs &a, int monoid)
+{
+    return a.has_by_value ? monoid_identity<T, W>(monoid) : acc_seed<T, W>(monoid);
+}
+
 template <typename T> __device__ __forceinline__ bool same_bits(T x, T y)
 {
     if constexpr (sizeof(T) == 1) return __builtin_bit_cast(uint8_t, x) == __builtin_bit_cast(uint8_t, y);

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
     const T *tval = (const T *)a.ct_val;
     const uint16_t *tloc = a.ct_loc;
     W *tl = (W *)a.tl_val;
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = pull_seed<T, W>(a, monoid);
     // (round 6, PullArgs::ct_mode: packed words -- slot << 19 | column - range base -- in tiles of CT_PACK_SLOTS slots; mode 2: one-byte value codes)
     const int packed = a.ct_mode;
     const int slots_rt = packed ? (CT_PACK_SLOTS < SLOTS ? CT_PACK_SLOTS : SLOTS) : SLOTS;

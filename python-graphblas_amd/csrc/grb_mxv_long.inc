@@ -391,7 +391,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_long_grp(const PullArgs a)
         }                                                                                           \
     } while (0)
     const bool ident_fold = monoid == OP_MIN || monoid == OP_MAX || monoid == OP_LOR || monoid == OP_LAND;
-    const T ident = from_acc<T, W>(monoid_identity<T, W>(monoid));
+    const T ident = from_acc<T, W>(pull_seed<T, W>(a, monoid));
     int64_t q = wv;
     if (q * 4 >= n_it) return;
     GRP_ITEM_LOADS(q);

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_mxv_pull(const PullArgs a)
 
     // ---- LDS: row accumulators at the monoid identity, row-start marks cleared -----------------------------------
     for (int k = tid; k <= nrows_t; k += PULL_BLOCK) {
-        s_tval[k] = monoid_identity<T, W>(monoid);
+        s_tval[k] = pull_seed<T, W>(a, monoid);
         s_thas[k] = 0;
     }
     for (int k = tid * 8; k < TILE + 8; k += PULL_BLOCK * 8) *(uint4 *)&s_head[k] = make_uint4(0u, 0u, 0u, 0u);

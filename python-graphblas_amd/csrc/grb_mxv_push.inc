@@ -190,7 +190,7 @@ __device__ __forceinline__ void push_chunk(const PushThin &a, int64_t q, int lan
             if (!ok) continue;
         }
         if constexpr (PASS == 0) {
-            t_val[j] = monoid_identity<T, W>(a.monoid);
+            t_val[j] = acc_seed<T, W>(a.monoid);
             if constexpr (SMALL) a.done_bits[j >> 6] = 0ull;  // (every writer of a word stores the same value)
         } else if constexpr (PASS == 1) {
             const T av = a.need_a ? ((const T *)a.aval)[a.a_iso ? 0 : p] : (T)0;

@@ -49,7 +49,7 @@ __device__ __forceinline__ void rows_group(const PullArgs &a, int64_t g, int lan
     int long_slot = 0;
     if (longw) long_slot = a.long_prefix[g] + __popcll(longw & ((1ull << lane) - 1ull));
     bool t_has = false;
-    W t_acc = monoid_identity<T, W>(monoid);
+    W t_acc = pull_seed<T, W>(a, monoid);
     if (is_long) {
         t_has = a.tl_has[long_slot] != 0;
         t_acc = acc_from_stored<W>(((const W *)a.tl_val)[long_slot], a.tl_ord != 0);
@@ -69,8 +69,8 @@ __device__ __forceinline__ void rows_group(const PullArgs &a, int64_t g, int lan
     //  ds_min_u32 / ds_max_u32 -- atomicMin on a float in LDS compiles to a read, a compare and a compare-and-swap LOOP, four of
     //  them per group and lane)
     const bool acc_ord = acc_is_ordered<W>(monoid);
-    acc_slots[lane] = acc_to_stored<W>(monoid_identity<T, W>(monoid), acc_ord);
-    acc_slots[64 + lane] = acc_to_stored<W>(monoid_identity<T, W>(monoid), acc_ord);
+    acc_slots[lane] = acc_to_stored<W>(pull_seed<T, W>(a, monoid), acc_ord);
+    acc_slots[64 + lane] = acc_to_stored<W>(pull_seed<T, W>(a, monoid), acc_ord);
     has_slots[lane] = 0;
     has_slots[64 + lane] = 0;
 

@@ -188,15 +188,15 @@ __global__ __launch_bounds__(HEAD ? TAG_HEAD_BLOCK : ROWS_BLOCK, HEAD ? 8 : 1) v
         old_val[k] = (need_old && in[k] && !(GRB_TAG_ABL & 16)) ? ((const T *)a.w_old_val)[row] : (T)0;
         is_long[k] = live[k] && ((longw[k] >> lane) & 1ull);
         t_has[k] = false;
-        t_acc[k] = monoid_identity<T, W>(monoid);
+        t_acc[k] = pull_seed<T, W>(a, monoid);
         act_me[k] = (actw[k] >> lane) & 1ull;
         // (a group without an active short row reads none of its entries; long_tails: long rows hold their cold entries here too)
         any_active[k] = live[k] && (actw[k] & nonempty[k] & (a.long_tails ? ~0ull : ~longw[k])) != 0;
-        s_acc[wave][k][lane] = monoid_identity<T, W>(monoid);
+        s_acc[wave][k][lane] = pull_seed<T, W>(a, monoid);
         s_off[wave][k][lane] = act_me[k] ? 0u : 0xffffffffu;
         s_has[wave][k][lane] = 0;
         if (lane == 0) {
-            s_acc[wave][k][64] = monoid_identity<T, W>(monoid);
+            s_acc[wave][k][64] = pull_seed<T, W>(a, monoid);
             s_off[wave][k][64] = 0u;  // (padding entries carry column -1 themselves)
             s_has[wave][k][64] = 0;
         }

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(RT_BLOCK, (ROWS4 <= 8192 && sizeof(T) == 4) ? GRB_R
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool snt = a.stream_nt != 0;  // (wave-uniform: a large matrix streams non-temporal, grb_mxv_common.inc)
     const bool need_old = (a.accum >= 0) || a.fresh;
-    const W ident = monoid_identity<T, W>(monoid);
+    const W ident = pull_seed<T, W>(a, monoid);
     const __amdgpu_buffer_rsrc_t xval_rs = make_rsrc(a.u_val, a.x_len * (int64_t)sizeof(T));
     const __amdgpu_buffer_rsrc_t col_rs = make_rsrc(a.rt_col, a.rt_units * 16);
     const __amdgpu_buffer_rsrc_t tag_rs = make_rsrc(a.rt_tag, a.rt_units * 8);

@@ -257,7 +257,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_strip(const PullArgs a)
     W *tl = (W *)a.tl_val;
     const bool masked = a.has_mask != 0;
     const bool by_has = monoid == OP_ANY;  // ANY has no identity: presence travels with the value
-    const T ident = from_acc<T, W>(monoid_identity<T, W>(monoid));
+    const T ident = from_acc<T, W>(pull_seed<T, W>(a, monoid));
     const unsigned long long le = lanes_le(lane);
 
     int n_c[EPL];
@@ -712,7 +712,13 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_hstrip(const PullArgs a)
             if (g < n_fill) *(uint4 *)((char *)s_x + (size_t)g * 16) = piece[it];
         }
     }
-    if (threadIdx.x == 0) ((T *)s_x)[PAD] = MULT_CT == OP_TIMES ? (T)0 : monoid_identity<T, W>(MONOID_CT);
+    // (the padding slot: its products must not move an accumulator.  Integers: 0 for times, the identity for plus (value 0 + identity).
+    //  Floating point: the accumulators start at acc_seed -- NaN for min / max, which a NaN padding product (value + NaN) leaves alone;
+    //  -0.0 for plus, which a -0.0 padding product (0 * -0.0) leaves alone; +inf would turn a row of NaN products into +inf)
+    if (threadIdx.x == 0) {
+        if constexpr (std::is_floating_point<T>::value) ((T *)s_x)[PAD] = MULT_CT == OP_TIMES ? -(T)0 : (T)__builtin_nan("");
+        else ((T *)s_x)[PAD] = MULT_CT == OP_TIMES ? (T)0 : monoid_identity<T, W>(MONOID_CT);
+    }
     __syncthreads();
 
     (void)chunks_total;
@@ -722,7 +728,9 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_hstrip(const PullArgs a)
     W *tl = (W *)a.tl_val;
     const bool masked = a.has_mask != 0;
     const uint32_t unmasked_bit = masked ? 0u : 1u;
-    const T ident = monoid_identity<T, W>(MONOID_CT);
+    // (acc_seed even under the absorbing fill: a padding or NaN product is dropped by fmin / fmax, and the accumulators this kernel
+    //  sends to -- tl, seeded by k_long_init -- keep the fill's identity; a compile-time NaN also folds the first fmin away)
+    const T ident = acc_seed<T, W>(MONOID_CT);
     // Every stream of the chunk loop is read through a buffer descriptor over MY CLASS's part of it, with 32-bit offsets from the
     // class's first chunk (the host checks that a class stays below 2 GiB): a load that has nothing to read -- a step behind my last
     // chunk, a lane the mask switches off -- is issued all the same, with an offset beyond the descriptor (it returns 0 and moves no
@@ -811,7 +819,13 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_hstrip(const PullArgs a)
 #pragma unroll
             for (int i = 0; i < EPL; i++) {
                 const T av = s_dict[((i < 4 ? c0 : c1) >> (8 * (i & 3))) & 0xffu];  // (code 0 of a padding entry: any finite value -- x is the absorbing word)
-                acc = apply_binop<T>(MONOID_CT, acc, apply_binop<T>(MULT_CT, av, x[i]));
+                T prod = apply_binop<T>(MULT_CT, av, x[i]);
+                if constexpr (MULT_CT == OP_TIMES) {
+                    // (a padding entry's value is code 0, of either sign: its product is set to -0.0, the sum's seed, by the slot)
+                    const uint32_t sl = (i & 1) ? (r.c[i >> 1] >> 16) : (r.c[i >> 1] & 0xffffu);
+                    if (sl == (uint32_t)PAD) prod = -(T)0;
+                }
+                acc = apply_binop<T>(MONOID_CT, acc, prod);
             }
         } else {
 #pragma unroll

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(PULL_BLOCK) void k_mxv_seams(const PullArgs a)
     const int64_t row = a.tile_row[tile];
     const int64_t t_s = (row + a.rowptr[row]) / TILE;
     const W *cv = (const W *)a.carry_val;
-    W acc = monoid_identity<T, W>(monoid);
+    W acc = pull_seed<T, W>(a, monoid);
     int has = 0;
     for (int64_t t = t_s + lane; t < tile; t += 64) {
         if (a.carry_has[t]) {

@@ -101,6 +101,24 @@ GRB_HD W monoid_identity(int op)
     }
 }
 
+// the starting value of an ACCUMULATOR of monoid `op` (not the identity a user sees): the identity, except where the identity can
+// absorb an operand of the fold -- floating-point PLUS starts at -0.0 (-0 + x == x for every x, +0 included: a sum of -0.0 stays
+// -0.0), MIN / MAX at NaN (fmin(NaN, x) == x, fmin(NaN, NaN) == NaN: a fold that only met NaN products is NaN, not +-inf).  MAX
+// starts at -NaN so that its ordered-integer code (ord_of) lies below that of -inf, MIN at +NaN above +inf.
+template <typename T, typename W>
+GRB_HD W acc_seed(int op)
+{
+    if constexpr (std::is_same<T, float>::value || std::is_same<T, double>::value) {
+        switch (op) {
+        case OP_PLUS: return (W)-(T)0;
+        case OP_MIN: return (W)(std::is_same<T, float>::value ? __builtin_nanf("") : __builtin_nan(""));
+        case OP_MAX: return (W)(std::is_same<T, float>::value ? -__builtin_nanf("") : -__builtin_nan(""));
+        default: break;
+        }
+    }
+    return monoid_identity<T, W>(op);
+}
+
 // monoid terminal ("annihilator") test used for early exit: lor->true, land->false, any->anything
 template <typename T>
 GRB_HD bool monoid_is_terminal(int op, T v)
@@ -216,14 +234,34 @@ __device__ __forceinline__ void atomic_combine_cas(W *slot, W v, int monoid)
     }
 }
 
+// slot = fmin(slot, v) / fmax(slot, v) for a v that is not NaN: a NaN slot (the accumulator's seed, acc_seed) takes v.  (HIP's
+// atomicMin / atomicMax on float keep a NaN slot: their loop stores only while slot > v / slot < v)
+template <typename W>
+__device__ __forceinline__ void atomic_fminmax(W *slot, W v, bool is_min)
+{
+    using U = typename std::conditional<sizeof(W) == 4, unsigned int, unsigned long long>::type;
+    U *p = (U *)slot;
+    U old = *p;
+    while (true) {
+        const W o = __builtin_bit_cast(W, old);
+        if (!(o != o || (is_min ? v < o : v > o))) return;
+        const U prev = atomicCAS(p, old, __builtin_bit_cast(U, v));
+        if (prev == old) return;
+        old = prev;
+    }
+}
+
 template <typename W>
 __device__ __forceinline__ void atomic_combine(W *slot, W v, int monoid)
 {
     if constexpr (std::is_same<W, float>::value || std::is_same<W, double>::value) {
         switch (monoid) {
         case OP_PLUS: atomicAdd(slot, v); return;
-        case OP_MIN: if (v == v) atomicMin(slot, v); return;  // fmin semantics: a NaN operand is ignored
-        case OP_MAX: if (v == v) atomicMax(slot, v); return;
+        // fmin semantics: a NaN operand is ignored.  HIP's atomicMin / atomicMax stay on the fast path (a compare-and-swap loop for
+        // float, the hardware instruction for double on gfx950); they do not replace a NaN slot (the accumulator's seed, acc_seed)
+        // everywhere, so a slot that was NaN before is finished by atomic_fminmax -- once per slot, at its first value
+        case OP_MIN: if (v == v) { const W o = atomicMin(slot, v); if (o != o) atomic_fminmax<W>(slot, v, true); } return;
+        case OP_MAX: if (v == v) { const W o = atomicMax(slot, v); if (o != o) atomic_fminmax<W>(slot, v, false); } return;
         default: atomic_combine_cas<W>(slot, v, monoid); return;
         }
     } else if constexpr (std::is_same<W, int32_t>::value) {

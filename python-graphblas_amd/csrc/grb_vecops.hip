@@ -71,7 +71,7 @@ __global__ void k_fill_one(W *p, W v)
     if (blockIdx.x == 0 && threadIdx.x == 0) p[0] = v;
 }
 
-// out[0] = monoid-fold of the present values (out starts at the identity)
+// out[0] = monoid-fold of the present values (out[0] starts at the accumulator seed, out[1] at 0)
 template <typename T>
 __global__ void k_reduce(const T *val, const uint64_t *bits, int64_t n, int monoid, typename Widen<T>::type *out)
 {
@@ -119,6 +119,7 @@ __global__ void k_reduce(const T *val, const uint64_t *bits, int64_t n, int mono
         if (th) {
             if (monoid == OP_ANY) out[0] = t;
             else atomic_combine<W>(out, t, monoid);
+            out[1] = (W)1;  // (out[1]: "some value was folded in" -- every writer stores the same word)
         }
     }
 }
@@ -237,12 +238,17 @@ static void reduce_to(T *val, const GB_BinaryOp_opaque *accum, const GB_Monoid_o
                 cast_array(mt, cast_buf.p, u->type->code, u->d_val, (int64_t)u->n);
                 src = cast_buf.p;
             }
-            DevBuf<W> out(1);
-            hipLaunchKernelGGL((k_fill_one<W>), dim3(1), dim3(64), 0, ctx().stream, out.p, h);
+            DevBuf<W> out(2);
+            // (the slot starts at the accumulator seed, not the identity: a sum of -0.0 stays -0.0, a min / max over NaN alone is NaN;
+            //  out[1] says whether any value came in -- an empty vector keeps the identity)
+            hipLaunchKernelGGL((k_fill_one<W>), dim3(1), dim3(64), 0, ctx().stream, out.p, acc_seed<TM, W>(op));
+            hipLaunchKernelGGL((k_fill_one<W>), dim3(1), dim3(64), 0, ctx().stream, out.p + 1, (W)0);
             const int64_t blocks = std::min<int64_t>(ceil_div((int64_t)bits_words64(u->n), 256), (int64_t)ctx().num_cus * 4);
             hipLaunchKernelGGL((k_reduce<TM>), dim3((unsigned)blocks), dim3(256), 0, ctx().stream, (const TM *)src,
                                (const uint64_t *)u->d_bits, (int64_t)u->n, op, out.p);
-            d2h(&h, out.p, sizeof(W));
+            W res[2];
+            d2h(res, out.p, sizeof(res));
+            if (res[1] != (W)0) h = res[0];
         }
         const TM r = std::is_same<TM, bool>::value ? (TM)(h != (W)0) : (TM)h;
         t = cast_value<T, TM>(r);

@@ -2,6 +2,7 @@
 import numpy as np
 
 from oracle import grb_oracle as O
+from tests.values import same_fp
 
 
 def o_obj(spec):
@@ -40,5 +41,7 @@ def same(got, exp_spec, rtol=0.0):
     assert got.tname == exp.tname, (got.tname, exp.tname)
     if rtol:
         np.testing.assert_allclose(gv, ev, rtol=rtol)
+    elif np.asarray(ev).dtype.kind == "f":
+        same_fp(np.asarray(gv), np.asarray(ev))  # (bit patterns: NaN matches NaN, the zero sign is compared)
     else:
         assert gv.tolist() == ev.tolist(), (gv, ev)

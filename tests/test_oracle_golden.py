@@ -10,6 +10,7 @@ import pytest
 from oracle import dense_eval as D
 from oracle import grb_oracle as O
 from tests.helpers import o_obj, oracle_case, same
+from tests.values import rand_vals, same_values
 
 _G = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_literals.json")))
 
@@ -187,6 +188,62 @@ def test_oracle_vs_dense_bruteforce(semiring, seed):
     got3 = O.vxm(_ovec(rv, rh, tname), _omat(Bv, Bh, tname), semiring)
     exp3 = _ovec(Tv2[0], Th2[0], tname)
     assert got3.idx.tolist() == exp3.idx.tolist() and got3.vals.tolist() == exp3.vals.tolist()
+
+
+def _rand_dense_domain(rng, shape, density, tname, domain):
+    has = rng.random(shape) < density
+    val = np.zeros(shape, O.NP_OF[tname])
+    val[has] = rand_vals(rng, int(has.sum()), tname, domain)
+    return val, has
+
+
+@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("domain", ["signed", "special"])
+@pytest.mark.parametrize("semiring", SEMIRINGS)
+def test_oracle_vs_dense_bruteforce_value_domains(semiring, domain, seed):
+    """The C oracle against the naive dense restatement over the value domains of tests/values.py: full-range integers, and for the
+    floating-point types NaN, +-inf, +-0.0, subnormals and +-MAX (both fold in column order, so even inexact sums agree bit for bit),
+    with a floating-point value mask (-0.0 false, NaN true) -- compared with the strict comparator."""
+    rng = np.random.default_rng(5000 + 1000 * seed + sum(map(ord, semiring + domain)))
+    monoid, mult = semiring.split("_", 1)
+    if monoid in ("lor", "land", "lxor", "lxnor"):
+        tname = "BOOL"
+    elif domain == "special":
+        tname = ["FP32", "FP64"][seed % 2]
+    else:
+        tname = ["INT8", "UINT64", "INT16", "UINT32", "INT32", "UINT8", "INT64", "UINT16", "FP32", "FP64"][(seed + len(semiring)) % 10]
+    np_t = O.NP_OF[tname]
+    dom = "signed" if tname == "BOOL" else domain
+    m, k, n = (int(x) for x in rng.integers(1, 9, 3))
+    Av, Ah = _rand_dense_domain(rng, (m, k), 0.6, tname, dom)
+    Bv, Bh = _rand_dense_domain(rng, (k, n), 0.6, tname, dom)
+    Cv, Ch = _rand_dense_domain(rng, (m, n), 0.4, tname, dom)
+    Mv, Mh = _rand_dense_domain(rng, (m, n), 0.6, "FP32", "special")
+    comp, struct, replace = (bool(x) for x in rng.integers(0, 2, 3))
+    accum = [None, "plus", "min", "max", "second"][seed % 5] if tname != "BOOL" else [None, "lor", "land"][seed % 3]
+    Tv, Th = D.matmul(Av, Ah, Bv, Bh, monoid, mult, np_t)
+    Nv, Nh = D.write(Cv, Ch, Tv, Th, Mv, Mh, comp=comp, struct=struct, accum=accum, replace=replace, np_t=np_t)
+    got = O.mxm(_omat(Av, Ah, tname), _omat(Bv, Bh, tname), semiring, C=_omat(Cv, Ch, tname), mask=_omat(Mv, Mh, "FP32"),
+                mask_comp=comp, mask_struct=struct, accum=accum, replace=replace)
+    exp = _omat(Nv, Nh, tname)
+    assert got.indptr.tolist() == exp.indptr.tolist()
+    same_values(got.indices, got.values, exp.indices, exp.values, None, ("mxm", tname, semiring, domain))
+    uv, uh = Bv[:, 0], Bh[:, 0]
+    Tv1, Th1 = D.matmul(Av, Ah, uv[:, None], uh[:, None], monoid, mult, np_t)
+    Nv1, Nh1 = D.write(Cv[:, 0], Ch[:, 0], Tv1[:, 0], Th1[:, 0], Mv[:, 0], Mh[:, 0], comp=comp, struct=struct, accum=accum,
+                       replace=replace, np_t=np_t)
+    got = O.mxv(_omat(Av, Ah, tname), _ovec(uv, uh, tname), semiring, w=_ovec(Cv[:, 0], Ch[:, 0], tname),
+                mask=_ovec(Mv[:, 0], Mh[:, 0], "FP32"), mask_comp=comp, mask_struct=struct, accum=accum, replace=replace)
+    exp = _ovec(Nv1, Nh1, tname)
+    same_values(got.idx, got.vals, exp.idx, exp.vals, None, ("mxv", tname, semiring, domain))
+    # the oracle's reduce against the dense fold (no identity for a non-empty set)
+    if tname != "BOOL" and Ah[0].any():
+        for mon in ("plus", "times", "min", "max"):
+            acc = None
+            for x in Av[0][Ah[0]]:
+                acc = x if acc is None else D.binop(mon, acc, x, np_t)
+            ref = O.vec_reduce(_ovec(Av[0], Ah[0], tname), mon)
+            same_values([0], np.array([ref], np_t), [0], np.array([acc], np_t), None, ("reduce", tname, mon, domain))
 
 
 def test_scipy_crosscheck_plus_times():
