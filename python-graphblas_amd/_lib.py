@@ -116,7 +116,14 @@ def _declare(L):
         getattr(L, f"GrB_Vector_extractElement_{t}").argtypes = [P(ct), c_void_p, c_u64]
         getattr(L, f"GrB_Vector_assign_{t}").argtypes = [c_void_p, c_void_p, c_void_p, ct, c_void_p, c_u64, c_void_p]
         getattr(L, f"GrB_Vector_reduce_{t}").argtypes = [P(ct), c_void_p, c_void_p, c_void_p, c_void_p]
+        getattr(L, f"GrB_Scalar_setElement_{t}").argtypes = [c_void_p, ct]
+        for kind in ("Matrix", "Vector"):  # (C, Mask, accum, op, A, y, desc)
+            getattr(L, f"GrB_{kind}_select_{t}").argtypes = [c_void_p] * 5 + [ct, c_void_p]
     L.GrB_Vector_resize.argtypes = [c_void_p, c_u64]
+    L.GrB_Matrix_select_Scalar.argtypes = [c_void_p] * 7
+    L.GrB_Vector_select_Scalar.argtypes = [c_void_p] * 7
+    L.GrB_Scalar_new.argtypes = [P(c_void_p), c_void_p]
+    L.GrB_Scalar_free.argtypes = [P(c_void_p)]
     for t in TYPE_NAMES:
         getattr(L, f"GrB_Matrix_build_{t}").argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]
         getattr(L, f"GrB_Matrix_extractTuples_{t}").argtypes = [c_void_p, c_void_p, c_void_p, P(c_u64), c_void_p]

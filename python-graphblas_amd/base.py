@@ -10,6 +10,10 @@ Mirrors, for the mxm/mxv/vxm path, the reference's
 """
 from __future__ import annotations
 
+import ctypes
+
+import numpy as np
+
 from . import _lib
 from .descriptor import lookup as descriptor_lookup
 from .dtypes import BOOL, lookup_dtype
@@ -171,6 +175,12 @@ class BaseType:
         """reference core/base.py:338-514."""
         if isinstance(expr, InfixMatMul):
             expr = expr.with_op(semiring.plus_times)
+        if isinstance(expr, MaskSelect):
+            # ``C(...) << A.select(M.S)`` (reference core/vector.py:86-99, _select_mask): without a mask of its own the update takes the
+            # selecting mask (and replaces, unless it accumulates); with one, the masked copy is made first
+            if mask is None:
+                return self._update(expr.parent, mask=expr.mask, accum=accum, replace=accum is None, opts=opts)
+            return self._update(expr.parent.dup(mask=expr.mask), mask=mask, accum=accum, replace=replace, opts=opts)
         if isinstance(expr, Scalar) or _is_python_scalar(expr):
             # ``w(mask) << 5``: scalar assign over every index (reference core/base.py:352-372 -> Updater[...] << scalar)
             return self._assign_scalar_all(expr, mask=mask, accum=accum, replace=replace, opts=opts)
@@ -424,13 +434,14 @@ class Expression:
     """A delayed C call: which function, which operator, which operands (reference
     VectorExpression/MatrixExpression, core/vector.py:2166+, core/matrix.py:3621+)."""
 
-    def __init__(self, method_name, cfunc_name, args, *, op, output_type, shape, at=False, bt=False):
+    def __init__(self, method_name, cfunc_name, args, *, op, output_type, shape, at=False, bt=False, dtype=None):
         self.method_name, self.cfunc_name, self.args, self.op = method_name, cfunc_name, args, op
         self.output_type, self.shape, self.at, self.bt = output_type, shape, at, bt
+        self._dtype = dtype  # (select: the result has the input's type, not the operator's BOOL)
 
     @property
     def dtype(self):
-        return self.op.return_type
+        return self._dtype if self._dtype is not None else self.op.return_type
 
     def new(self, dtype=None, *, mask=None, name=None, **opts):
         """Allocate the output, then the same update path (reference core/base.py:583-616)."""
@@ -445,6 +456,77 @@ class Expression:
     def _force_library_error(self):
         # shape mismatches are raised BY THE LIBRARY (reference core/matrix.py:2260-2261)
         self.new()
+
+
+class MaskSelect:
+    """``A.select(M.S)`` / ``A.select(M.V)``: the entries of ``A`` the mask lets through -- what ``A.dup(mask=M.S)`` gives."""
+
+    def __init__(self, parent, mask):
+        self.parent, self.mask = parent, mask
+        self.dtype, self.shape, self.output_type = parent.dtype, parent.shape, type(parent)
+
+    def new(self, dtype=None, *, mask=None, name=None, **opts):
+        out = self.output_type(lookup_dtype(dtype) if dtype is not None else self.dtype, *self.shape, name=name)
+        if mask is None:
+            out._update(self, opts=opts)
+        else:
+            out(mask=mask, **opts).update(self)
+        return out
+
+
+class GrBScalarArg:
+    """A ``GrB_Scalar`` made from a host-side :class:`Scalar` for the length of one call (the ``_Scalar`` entry points); an empty
+    Scalar stays empty, and the library answers it with ``GrB_EMPTY_OBJECT``."""
+
+    def __init__(self, scalar):
+        self.name = scalar.name
+        self._handle = ctypes.c_void_p()
+        L = _lib.load()
+        check_status(L.GrB_Scalar_new(ctypes.byref(self._handle), scalar.dtype._carg), None)
+        if not scalar.is_empty:
+            check_status(getattr(L, f"GrB_Scalar_setElement_{scalar.dtype.name}")(self._handle, scalar.value), None)
+
+    @property
+    def _carg(self):
+        return self._handle
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value and _lib is not None and _lib.lib is not None:
+            try:
+                _lib.lib.GrB_Scalar_free(ctypes.byref(h))
+            except Exception:  # interpreter shutdown
+                pass
+
+
+def select_expression(x, op, thunk, *, output_type, shape, at=False):
+    """``x.select(op, thunk)`` for a Matrix / TransposedMatrix / Vector ``x`` (reference core/matrix.py:2597-2623, core/vector.py select):
+    the delayed call of ``GrB_<kind>_select_<thunk dtype>``, or of the ``_Scalar`` form for a :class:`Scalar` thunk."""
+    base = x._matrix if hasattr(x, "_matrix") else x
+    kind = base._grb_kind
+    if isinstance(op, Mask):
+        if thunk is not None:
+            raise TypeError("thunk may not be given together with a mask: a mask selects by itself")
+        if at:
+            raise TypeError("select by a mask is not available on a transposed matrix: use A.T.new().select(mask)")
+        _check_mask(op, base)
+        return MaskSelect(base, op)
+    if thunk is None:
+        thunk = False  # (the reference's default, core/matrix.py:2616)
+    if isinstance(thunk, Scalar):
+        tdtype, carg, suffix = thunk.dtype, GrBScalarArg(thunk), "Scalar"
+    elif isinstance(thunk, (bool, np.bool_)):
+        tdtype, carg, suffix = BOOL, bool(thunk), "BOOL"
+    elif isinstance(thunk, (int, float, np.integer, np.floating)):
+        tdtype = lookup_dtype(np.int64 if isinstance(thunk, int) else (np.float64 if isinstance(thunk, float) else np.asarray(thunk).dtype))
+        if isinstance(thunk, int) and not -(1 << 63) <= thunk < (1 << 63):
+            tdtype = lookup_dtype(np.uint64)
+        carg, suffix = tdtype.np_type.type(thunk).item(), tdtype.name
+    else:
+        raise TypeError(f"Bad type for argument `thunk` in {kind}.select(...): {type(thunk).__name__}; expected a number or a Scalar")
+    top = get_typed_op(op, base.dtype, tdtype, kind="select")
+    return Expression("select", f"GrB_{kind}_select_{suffix}", [base, carg], op=top, output_type=output_type, shape=shape, at=at,
+                      dtype=base.dtype)
 
 
 class InfixMatMul:

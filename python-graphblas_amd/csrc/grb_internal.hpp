@@ -37,6 +37,16 @@ enum OpCode : int {
 };
 inline bool op_is_comparison(int op) { return op >= OP_EQ && op <= OP_LE; }
 
+// the builtin index-unary operators that return BOOL (GrB_select; grb_select.hip) have a code space of their own, above OP_UNSUPPORTED:
+// canonical_op rejects them wherever a binary operator is expected.  ROWINDEX / COLINDEX / DIAGINDEX (apply operators) stay OP_UNSUPPORTED
+enum SelOp : int {
+    SEL_TRIL = 2000, SEL_TRIU, SEL_DIAG, SEL_OFFDIAG, SEL_COLLE, SEL_COLGT, SEL_ROWLE, SEL_ROWGT,
+    SEL_VALUEEQ, SEL_VALUENE, SEL_VALUEGT, SEL_VALUEGE, SEL_VALUELT, SEL_VALUELE
+};
+inline bool op_is_select(int op) { return op >= SEL_TRIL && op <= SEL_VALUELE; }
+inline bool sel_is_value(int op) { return op >= SEL_VALUEEQ && op <= SEL_VALUELE; }
+constexpr uint64_t MAGIC_SCALAR = 0x4752425343414c52ULL;  // "GRBSCALR"
+
 constexpr uint64_t MAGIC_VECTOR = 0x4752425645435452ULL;  // "GRBVECTR"
 constexpr uint64_t MAGIC_MATRIX = 0x4752424d41545258ULL;  // "GRBMATRX"
 constexpr uint64_t MAGIC_FREED = 0xdeadbeefdeadbeefULL;
@@ -196,6 +206,7 @@ void preload_mxm();
 void preload_vecops();
 void preload_object();
 void preload_prim();
+void preload_select();
 
 template <typename T>
 struct DevPtr {  // owner of a device block that a callee allocated (freed unless released)
@@ -239,6 +250,18 @@ struct GB_Semiring_opaque {
     int mult;
     int type;
     const char *name;
+};
+struct GB_IndexUnaryOp_opaque {
+    int op;    // SelOp, or OP_UNSUPPORTED
+    int type;  // the type entry and thunk are compared in (value operators); INT64 for the positional ones
+    const char *name;
+};
+struct GB_Scalar_opaque {  // host side: a value + presence (grb_surface.hip)
+    uint64_t magic;
+    GrB_Type type;
+    bool has;
+    unsigned char value[8];
+    std::string err;
 };
 struct GB_Descriptor_opaque {
     bool replace, comp, structure, t0, t1;

@@ -3,11 +3,13 @@
 // An unmodified python-graphblas resolves, while it is imported, handles far outside mxm / mxv / vxm (graphblas/core/mask.py:1-5:
 // select.valuene, unary.one; core/operator/base.py:803-893: every GrB_* / GxB_* operator name it finds) and binds one C entry
 // point per operation.  This file makes those names exist:
-//   * builtin unary, index-unary and the remaining binary operators as DATA symbols.  The kernels implement none of them: every
-//     entry point that consumes an operator goes through canonical_op(), which rejects their codes with GrB_NOT_IMPLEMENTED;
+//   * builtin unary, index-unary and the remaining binary operators as DATA symbols.  The kernels implement none of the unary and
+//     extra binary ones: every entry point that consumes an operator goes through canonical_op(), which rejects their codes with
+//     GrB_NOT_IMPLEMENTED.  The index-unary operators that return BOOL (GrB_TRIL ... GrB_ROWGT, GrB_VALUE*_<T>) carry the SelOp
+//     codes GrB_select runs on (grb_select.hip); GrB_ROWINDEX / COLINDEX / DIAGINDEX_* are apply operators and stay handle-only;
 //   * GrB_Scalar for real (a host-side value + presence: the reference passes scalars by GrB_Scalar handle in C API 2.0 calls);
 //   * the entry points of the operations this library does not accelerate, with their C API 2.0 signatures, returning
-//     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.
+//     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -20,26 +22,14 @@ struct GB_UnaryOp_opaque {
     int type;
     const char *name;
 };
-struct GB_IndexUnaryOp_opaque {
-    int op;
-    int type;
-    const char *name;
-};
-constexpr uint64_t MAGIC_SCALAR = 0x4752425343414c52ULL;  // "GRBSCALR"
-struct GB_Scalar_opaque {
-    uint64_t magic;
-    GrB_Type type;
-    bool has;
-    unsigned char value[8];
-    std::string err;
-};
+// (GB_IndexUnaryOp_opaque and GB_Scalar_opaque: grb_internal.hpp -- grb_select.hip reads them)
 
 // ---- operator handles (data symbols) ----------------------------------------------------------------------------------
 #define DEF_UNOP(SYM, T)                                                    \
     static GB_UnaryOp_opaque uop_obj_##SYM = {OP_UNSUPPORTED, TC_##T, #SYM}; \
     extern "C" GrB_UnaryOp SYM = &uop_obj_##SYM;
-#define DEF_IDXOP(SYM, T)                                                        \
-    static GB_IndexUnaryOp_opaque iop_obj_##SYM = {OP_UNSUPPORTED, TC_##T, #SYM}; \
+#define DEF_IDXOP(SYM, CODE, T)                                         \
+    static GB_IndexUnaryOp_opaque iop_obj_##SYM = {CODE, TC_##T, #SYM}; \
     extern "C" GrB_IndexUnaryOp SYM = &iop_obj_##SYM;
 #define DEF_BINOP_X(SYM, OP, T)                                        \
     static GB_BinaryOp_opaque bopx_obj_##SYM = {OP, TC_##T, #SYM};     \
@@ -51,12 +41,12 @@ struct GB_Scalar_opaque {
     DEF_UNOP(GrB_ABS_##T, T)                     \
     DEF_UNOP(GxB_ONE_##T, T)                     \
     DEF_UNOP(GxB_LNOT_##T, T)                    \
-    DEF_IDXOP(GrB_VALUEEQ_##T, T)                \
-    DEF_IDXOP(GrB_VALUENE_##T, T)                \
-    DEF_IDXOP(GrB_VALUEGT_##T, T)                \
-    DEF_IDXOP(GrB_VALUEGE_##T, T)                \
-    DEF_IDXOP(GrB_VALUELT_##T, T)                \
-    DEF_IDXOP(GrB_VALUELE_##T, T)                \
+    DEF_IDXOP(GrB_VALUEEQ_##T, SEL_VALUEEQ, T)           \
+    DEF_IDXOP(GrB_VALUENE_##T, SEL_VALUENE, T)           \
+    DEF_IDXOP(GrB_VALUEGT_##T, SEL_VALUEGT, T)           \
+    DEF_IDXOP(GrB_VALUEGE_##T, SEL_VALUEGE, T)           \
+    DEF_IDXOP(GrB_VALUELT_##T, SEL_VALUELT, T)           \
+    DEF_IDXOP(GrB_VALUELE_##T, SEL_VALUELE, T)           \
     DEF_BINOP_X(GrB_DIV_##T, OP_UNSUPPORTED, T)  \
     DEF_BINOP_X(GxB_RDIV_##T, OP_UNSUPPORTED, T) \
     DEF_BINOP_X(GxB_RMINUS_##T, OP_RMINUS, T)    \
@@ -78,20 +68,20 @@ DEF_UNOP(GrB_BNOT_UINT8, UINT8)
 DEF_UNOP(GrB_BNOT_UINT16, UINT16)
 DEF_UNOP(GrB_BNOT_UINT32, UINT32)
 DEF_UNOP(GrB_BNOT_UINT64, UINT64)
-DEF_IDXOP(GrB_ROWINDEX_INT32, INT32)
-DEF_IDXOP(GrB_ROWINDEX_INT64, INT64)
-DEF_IDXOP(GrB_COLINDEX_INT32, INT32)
-DEF_IDXOP(GrB_COLINDEX_INT64, INT64)
-DEF_IDXOP(GrB_DIAGINDEX_INT32, INT32)
-DEF_IDXOP(GrB_DIAGINDEX_INT64, INT64)
-DEF_IDXOP(GrB_TRIL, INT64)
-DEF_IDXOP(GrB_TRIU, INT64)
-DEF_IDXOP(GrB_DIAG, INT64)
-DEF_IDXOP(GrB_OFFDIAG, INT64)
-DEF_IDXOP(GrB_COLLE, INT64)
-DEF_IDXOP(GrB_COLGT, INT64)
-DEF_IDXOP(GrB_ROWLE, INT64)
-DEF_IDXOP(GrB_ROWGT, INT64)
+DEF_IDXOP(GrB_ROWINDEX_INT32, OP_UNSUPPORTED, INT32)
+DEF_IDXOP(GrB_ROWINDEX_INT64, OP_UNSUPPORTED, INT64)
+DEF_IDXOP(GrB_COLINDEX_INT32, OP_UNSUPPORTED, INT32)
+DEF_IDXOP(GrB_COLINDEX_INT64, OP_UNSUPPORTED, INT64)
+DEF_IDXOP(GrB_DIAGINDEX_INT32, OP_UNSUPPORTED, INT32)
+DEF_IDXOP(GrB_DIAGINDEX_INT64, OP_UNSUPPORTED, INT64)
+DEF_IDXOP(GrB_TRIL, SEL_TRIL, INT64)
+DEF_IDXOP(GrB_TRIU, SEL_TRIU, INT64)
+DEF_IDXOP(GrB_DIAG, SEL_DIAG, INT64)
+DEF_IDXOP(GrB_OFFDIAG, SEL_OFFDIAG, INT64)
+DEF_IDXOP(GrB_COLLE, SEL_COLLE, INT64)
+DEF_IDXOP(GrB_COLGT, SEL_COLGT, INT64)
+DEF_IDXOP(GrB_ROWLE, SEL_ROWLE, INT64)
+DEF_IDXOP(GrB_ROWGT, SEL_ROWGT, INT64)
 
 // ---- GrB_Scalar -----------------------------------------------------------------------------------------------------
 static void check_scalar(const GB_Scalar_opaque *s, const char *what)
@@ -287,8 +277,6 @@ NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB
 NI_M(GrB_Matrix_removeElement, GrB_Index, GrB_Index)
 NI_M(GrB_Matrix_assign_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_Scalar, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
 NI_M(GrB_Matrix_setElement_Scalar, const GrB_Scalar, GrB_Index, GrB_Index)
-NI_V(GrB_Vector_select_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, const GrB_Scalar, const GrB_Descriptor)
-NI_M(GrB_Matrix_select_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Matrix, const GrB_Scalar, const GrB_Descriptor)
 NI_V(GrB_Vector_apply_BinaryOp1st_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Scalar, const GrB_Vector, const GrB_Descriptor)
 NI_V(GrB_Vector_apply_BinaryOp2nd_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, const GrB_Scalar, const GrB_Descriptor)
 NI_V(GrB_Vector_apply_IndexOp_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, const GrB_Scalar, const GrB_Descriptor)
@@ -326,8 +314,6 @@ extern "C" GrB_Info GrB_Semiring_new(GrB_Semiring *, GrB_Monoid, GrB_BinaryOp) {
     extern "C" GrB_Info GrB_Matrix_extractElement_##NAME(ctype *, const GrB_Matrix, GrB_Index, GrB_Index) { return GrB_NOT_IMPLEMENTED; } \
     extern "C" GrB_Info GrB_Matrix_reduce_##NAME(ctype *, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; } \
     NI_M(GrB_Matrix_assign_##NAME, const GrB_Matrix, const GrB_BinaryOp, ctype, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor) \
-    NI_V(GrB_Vector_select_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, ctype, const GrB_Descriptor) \
-    NI_M(GrB_Matrix_select_##NAME, const GrB_Matrix, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Matrix, ctype, const GrB_Descriptor) \
     NI_V(GrB_Vector_apply_BinaryOp1st_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, ctype, const GrB_Vector, const GrB_Descriptor) \
     NI_V(GrB_Vector_apply_BinaryOp2nd_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, ctype, const GrB_Descriptor) \
     NI_V(GrB_Vector_apply_IndexOp_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, ctype, const GrB_Descriptor) \

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .base import BaseType, Expression, InfixMatMul, call, call_on
+from .base import BaseType, Expression, InfixMatMul, call, call_on, select_expression
 from .dtypes import lookup_dtype
 from .exceptions import DimensionMismatch
 from .operators import get_typed_op, semiring as _semiring
@@ -335,6 +335,11 @@ class Matrix(BaseType):
         """``C << A.power(n, semiring)`` by repeated squaring (reference core/matrix.py:2840-2905)."""
         return _matrix_power(self, n, op)
 
+    def select(self, op, thunk=None):
+        """``C << A.select("tril", -1)`` / ``A.select(">=", 3)`` / ``A.select(M.S)``: the entries the index-unary operator (or the
+        mask) keeps (reference core/matrix.py:2597-2623 -> C ``GrB_Matrix_select_<T>``)."""
+        return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape)
+
     def __matmul__(self, other):
         return InfixMatMul(self, other)
 
@@ -376,6 +381,10 @@ class TransposedMatrix:
 
     def power(self, n, op=_semiring.plus_times):
         return _matrix_power(self, n, op)
+
+    def select(self, op, thunk=None):
+        """``A.T.select(op, thunk)``: the selection runs on the transpose (descriptor T0)."""
+        return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape, at=True)
 
     def __matmul__(self, other):
         return InfixMatMul(self, other)

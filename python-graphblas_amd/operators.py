@@ -9,6 +9,10 @@ Mirrors, for the builtin operators on the mxm/mxv/vxm path only, the reference's
 reduction or one semiring mat-vec (``agg.sum/prod/min/max/all/any/any_value/count/exists``, core/operator/agg.py:356-378) are
 here; user-defined functions, UDTs, composite aggregators and positional ops need a JIT and are outside the path
 (SURVEY.md section 2 #6).
+
+``select`` (alias ``indexunary`` for the same names) holds the builtin index-unary operators that return BOOL -- ``tril, triu, diag,
+offdiag, rowle, rowgt, colle, colgt, indexle, indexgt, valueeq, valuene, valuegt, valuege, valuelt, valuele`` -- for
+``A.select(op, thunk)`` (reference core/operator/select.py, indexunary.py; string spellings core/operator/utils.py:329-342).
 """
 from __future__ import annotations
 
@@ -190,6 +194,43 @@ class Semiring(_OpBase):
         return expr.with_op(self)
 
 
+_SELECT_POSITIONAL = {"tril": "TRIL", "triu": "TRIU", "diag": "DIAG", "offdiag": "OFFDIAG", "rowle": "ROWLE", "rowgt": "ROWGT",
+                      "colle": "COLLE", "colgt": "COLGT", "indexle": "ROWLE", "indexgt": "ROWGT"}  # a vector is a column: index = row
+_SELECT_VALUE = ["valueeq", "valuene", "valuegt", "valuege", "valuelt", "valuele"]
+_SELECT_SYMBOLS = {"==": "valueeq", "!=": "valuene", ">": "valuegt", ">=": "valuege", "<": "valuelt", "<=": "valuele",
+                   "col<=": "colle", "col>": "colgt", "row<=": "rowle", "row>": "rowgt", "index<=": "indexle", "index>": "indexgt"}
+
+
+class SelectOp(_OpBase):
+    """A builtin index-unary operator that returns BOOL.  The positional ones are typed INT64 whatever the collection's type (their
+    thunk is a diagonal / row / column number); the value ones compare entry and thunk in ``unify(A.dtype, thunk dtype)``."""
+
+    opclass = "SelectOp"
+
+    @property
+    def positional(self):
+        return self.name in _SELECT_POSITIONAL
+
+    def _coerce(self, dtype):
+        return _INT64 if self.positional else dtype
+
+    def _gb_candidates(self, dtype):
+        if self.positional:
+            return [f"GrB_{_SELECT_POSITIONAL[self.name]}"]
+        return [f"GrB_{self.name.upper()}_{dtype.name}"]
+
+    def __getitem__(self, dtype):
+        t = super().__getitem__(dtype)
+        t.return_type = BOOL
+        return t
+
+    def __call__(self, x, thunk=None):
+        """Functional form: ``select.tril(A, k)`` / ``select.rowle(v, 3)``."""
+        if not hasattr(x, "select"):
+            raise TypeError(f"Expected a Matrix or a Vector, got {type(x).__name__}")
+        return x.select(self, thunk)
+
+
 class _Namespace:
     def __init__(self, kind):
         self._kind = kind
@@ -203,6 +244,8 @@ monoid = _Namespace("monoid")
 semiring = _Namespace("semiring")
 op = _Namespace("op")
 agg = _Namespace("agg")
+select = _Namespace("select")
+indexunary = select  # (the same operator objects under the reference's other name for them)
 
 for _n in _BINARY_NAMES:
     setattr(binary, _n, BinaryOp(_n))
@@ -220,6 +263,9 @@ for _m in _MONOID_NAMES:
 
 from .dtypes import INT64 as _INT64  # noqa: E402
 
+for _n in [*_SELECT_POSITIONAL, *_SELECT_VALUE]:
+    setattr(select, _n, SelectOp(_n))
+
 for _a, _m in [("sum", "plus"), ("prod", "times"), ("all", "land"), ("any", "lor"), ("min", "min"), ("max", "max"),
                ("any_value", "any")]:
     setattr(agg, _a, Aggregator(_a, monoid=getattr(monoid, _m)))
@@ -229,6 +275,11 @@ agg.exists = Aggregator("exists", semiring=semiring.any_pair, any_dtype=_INT64)
 
 def _from_string(string, kind):
     s = string.strip()
+    if kind == "select":  # an operator's own name or a spelling of the reference's table, in either letter case
+        name = _SELECT_SYMBOLS.get(s.lower(), s.lower())
+        if name not in _SELECT_POSITIONAL and name not in _SELECT_VALUE:
+            raise ValueError(f"Unknown select string: {string!r}")
+        return getattr(select, name)
     if kind == "semiring":
         for sep in ("_", "."):
             if sep in s:
@@ -246,13 +297,17 @@ def _from_string(string, kind):
 
 def get_typed_op(op_, dtype, dtype2=None, *, kind=None):
     """reference core/operator/utils.py:60-157 restricted to builtin ops.  ``kind`` is "binary"
-    (accum: BinaryOp or Monoid, tests/test_vector.py:350-368) or "semiring"."""
+    (accum: BinaryOp or Monoid, tests/test_vector.py:350-368), "semiring" or "select"."""
     if isinstance(op_, TypedOp):
+        if (kind == "select") != (op_.opclass == "SelectOp"):
+            raise TypeError(f"Expected a {kind or 'binary'} operator; got {op_.opclass} `{op_!r}`")
         return op_
     if isinstance(op_, str):
-        op_ = _from_string(op_, "semiring" if kind == "semiring" else "binary")
+        op_ = _from_string(op_, kind if kind in ("semiring", "select") else "binary")
     if not isinstance(op_, _OpBase):
         raise TypeError(f"Unable to get typed operator from object with type {type(op_)}")
+    if (kind == "select") != isinstance(op_, SelectOp):
+        raise TypeError(f"Expected type: {'SelectOp' if kind == 'select' else 'BinaryOp, Monoid, Semiring'}; got {op_.opclass} `{op_!r}`")
     if kind == "semiring" and not isinstance(op_, Semiring):
         raise TypeError(f"Expected type: Semiring; got {op_.opclass} `{op_!r}`")
     if kind == "binary" and isinstance(op_, Semiring):

@@ -362,6 +362,13 @@ class Vector(BaseType):
 
         return self._ewise(other, op if op is not None else _binary.times, "ewise_mult", "GrB_Vector_eWiseMult")
 
+    def select(self, op, thunk=None):
+        """``w << v.select("==", 1)`` / ``v.select("index<=", 3)`` / ``v.select(m.V)`` (reference core/vector.py select -> C
+        ``GrB_Vector_select_<T>``).  A vector is a column: its index is the row."""
+        from .base import select_expression
+
+        return select_expression(self, op, thunk, output_type=Vector, shape=(self._size,))
+
     # ---- the hot path ---------------------------------------------------------------------------------------
     def vxm(self, other, op=_semiring.plus_times):
         """``w << u.vxm(A, semiring)``  (reference core/vector.py:1309-1378 -> C ``GrB_vxm``)."""
