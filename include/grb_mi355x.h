@@ -334,7 +334,21 @@ GrB_Info GrX_Vector_dup_as(GrB_Vector *w, const GrB_Type type, const GrB_Vector 
 GrB_Info GrX_Vector_fill_absent(GrB_Vector v, const GrB_Monoid monoid);
 /* Device bytes of the SpMV layouts cached with A so far (hot-coded columns, short part, long-row strips / items). */
 GrB_Info GrX_Matrix_cache_bytes(const GrB_Matrix A, uint64_t *bytes);
-/* Tuning / diagnostics knobs (also read from the environment at GrB_init as GRB_<NAME upper-case>):
+/* Tuning / diagnostics options.  Every one of them is also read from the environment at GrB_init, as GRB_<NAME in upper case> (the name
+ * is derived, not listed: "split_min_nnz", "lazy_min_nnz", "vec_pad_min_bytes", "mxm_masked_units_min_flops" and "mxm_bitmap_pool_cap",
+ * which had no environment name before the options moved into one table, have one now); a value that GrX_option_set would reject is
+ * reported on stderr and ignored.  GRB_DEBUG_FLAGS alone drops the bits it does not know instead.
+ *   GrX_option_set     stores a value (some options clamp or snap it, as described below) or returns GrB_INVALID_VALUE -- for a value the
+ *                      option does not take and for a name that is no option -- and leaves the option as it was
+ *   GrX_option_get     the value an option holds now (what GrX_option_set stored, not what it was given)
+ *   GrX_options_reset  every option back to what it held when GrB_init returned: the compiled default, or the environment's override.
+ *                      Options are process-global: whoever changes one for a call resets them after it.
+ *   "vec_pad_min_bytes"  vectors with at least this many bytes of values (default 1 Mi) are allocated with a front pad
+ *   "lean_min_nnz", "order_min_nnz", "stream_nt_min_nnz", "rows_head_min_groups": a negative value is stored as 0;
+ *   "split_min_len", "hub_min_len", "cold_in_rows" are moved into [0, 2^30], "long_sub" into [0, 16]
+ *   "mxm_masked_units_min_flops"  mask-driven products with fewer multiplies than this (default 64 Mi) keep the row kernels
+ *   "mxm_bitmap_min_cnt"  units of the symbolic SpGEMM pass with more entries than this (default 512) keep their bitmap for the numeric pass
+ *   "alloc_cache"   1 (default): freed device blocks are kept per size class and reused without a call of the HIP allocator; 0 releases them
  *   "debug_flags"   path selectors that keep results right: 128 no long/short row split, 256 no LDS bitmap in the symbolic
  *                   SpGEMM pass, 2048 no (presence, value) packing for BOOL, 65536 no row-length path for (monoid, PAIR) over a
  *                   full operand; any other bit is GrB_INVALID_VALUE.  The kernel ablation switches of the benchmark scripts
@@ -430,6 +444,8 @@ GrB_Info GrX_Matrix_cache_bytes(const GrB_Matrix A, uint64_t *bytes);
  *   "push_mode"     mxv/vxm direction: 0 always pull, 1 (default) push when u has fewer than n/64 entries and the
  *                   matrix indexed like u is at hand, 2 always push when possible */
 GrB_Info GrX_option_set(const char *name, int64_t value);
+GrB_Info GrX_option_get(const char *name, int64_t *value);
+GrB_Info GrX_options_reset(void);
 const char *GrX_version_string(void);
 
 /* ================================================================================================================

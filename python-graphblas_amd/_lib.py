@@ -148,6 +148,8 @@ def _declare(L):
     L.GrB_Vector_assign.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]
     L.GrB_Vector_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]
     L.GrX_option_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+    L.GrX_option_get.argtypes = [ctypes.c_char_p, P(ctypes.c_int64)]
+    L.GrX_options_reset.argtypes = []
     L.GrX_set_stream.argtypes = [c_void_p]
     L.GrX_synchronize.argtypes = []
     L.GrX_trim_memory.argtypes = []

@@ -4,7 +4,9 @@
 // mandatory -- there is no CPU fallback).
 #include <chrono>
 #include <algorithm>
+#include <cctype>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -13,7 +15,7 @@
 
 namespace grb {
 
-// "debug_flags": the shipped library only knows the switches that choose between two correct paths on the host side
+// The debug flags: the shipped library only knows the switches that choose between two correct paths on the host side
 // (128 no long/short row split, 256 no LDS bitmap in the symbolic SpGEMM pass, 2048 no (presence, value) packing, 65536 no
 // row-length path); the kernel ablation switches -- some of which make results wrong on purpose -- are compiled in by
 // -DGRB_ABLATE only (make ablate; the emulator build of the CPU test tier).
@@ -223,6 +225,109 @@ void d2d(void *dst, const void *src, size_t bytes)
 }
 void sync_stream() { GRB_HIP(hipStreamSynchronize(ctx().stream)); }
 
+// ---- the options (GrX_option_set / _get / GrX_options_reset, GRB_<NAME> in the environment): ONE row each ---------------------
+// A row names the option, the field of the context that holds it (an int or an int64_t: a value is cast to the field's type, as
+// ever) and what happens to a value before it is stored: ANY keeps it, WITHIN rejects it outside [lo, hi], ONE_OF rejects it unless it
+// is lo or hi, CLAMP moves it into [lo, hi].  A hook, for the few options that need more, runs after the rule: it may change the value
+// and rejects it by returning false.  include/grb_mi355x.h says what every option means, grb_internal.hpp holds the defaults.
+namespace {
+struct Option {
+    const char *name;
+    int Context::*i;
+    int64_t Context::*l;
+    enum Rule { ANY, WITHIN, ONE_OF, CLAMP } rule;
+    int64_t lo, hi;
+    bool (*hook)(int64_t &value);
+};
+using Hook = bool (*)(int64_t &);
+constexpr int64_t MAX64 = INT64_MAX, P30 = 1 << 30;
+constexpr Option opt(const char *n, int Context::*f, Option::Rule r = Option::ANY, int64_t lo = 0, int64_t hi = 0, Hook h = nullptr) { return {n, f, nullptr, r, lo, hi, h}; }
+constexpr Option opt(const char *n, int64_t Context::*f, Option::Rule r = Option::ANY, int64_t lo = 0, int64_t hi = 0, Hook h = nullptr) { return {n, nullptr, f, r, lo, hi, h}; }
+
+// kernel ablation switches exist in -DGRB_ABLATE builds only
+bool known_debug_flags(int64_t &v) { return !((int)v & ~DEBUG_FLAGS_MASK); }
+// (2 = sliced ELLPACK, 3 = persistent row groups with an LDS head, 4 = a lane per row: measured slower in rounds 1-2, removed)
+bool short_kernel_exists(int64_t &v) { return v != 2 && v != 3 && v != 4; }
+bool snap_long_classes(int64_t &v) { if (v != 16 && v != 32 && v != 64) v = 8; return true; }
+bool window_group(int64_t &v) { return (v & (v - 1)) == 0; }  // (0, 1, 2, 4, 8)
+bool release_cache_when_off(int64_t &v) { if (!v) dev_cache_release(); return true; }
+
+const Option OPTIONS[] = {
+    opt("debug_flags", &Context::debug_flags, Option::ANY, 0, 0, known_debug_flags),
+    opt("pull_ipt", &Context::tune_pull_ipt),
+    opt("hot_min_cols", &Context::hot_min_cols),
+    opt("hot_k", &Context::hot_k),
+    opt("push_mode", &Context::push_mode),
+    opt("split_min_nnz", &Context::split_min_nnz),
+    opt("split_min_len", &Context::split_min_len, Option::CLAMP, 0, P30),
+    opt("short_kernel", &Context::short_kernel, Option::WITHIN, 0, 6, short_kernel_exists),
+    opt("lazy_layout", &Context::lazy_layout),
+    opt("lazy_min_nnz", &Context::lazy_min_nnz),
+    opt("lean_min_nnz", &Context::lean_min_nnz, Option::CLAMP, 0, MAX64),
+    opt("long_kernel", &Context::long_kernel),
+    opt("long_classes", &Context::long_classes, Option::ANY, 0, 0, snap_long_classes),
+    opt("long_sub", &Context::long_sub, Option::CLAMP, 0, 16),
+    opt("long_sub_min_len", &Context::long_sub_min_len),
+    opt("mxm_mask_mode", &Context::mxm_mask_mode),
+    opt("mat_write_kernel", &Context::mat_write_kernel, Option::WITHIN, 0, 1),
+    opt("mxm_heavy_kernel", &Context::mxm_heavy_kernel),
+    opt("drop_hot_cols", &Context::drop_hot_cols),
+    opt("mxm_unit_min_flops", &Context::mxm_unit_min_flops),
+    opt("mxm_unit_min_per_window", &Context::mxm_unit_min_per_window),
+    opt("mxm_masked_units_min_flops", &Context::mxm_masked_units_min_flops),
+    opt("mxm_unit_small", &Context::mxm_unit_small, Option::WITHIN, 1, P30),  // (class limits of the SpGEMM units: entry counts)
+    opt("mxm_unit_mid", &Context::mxm_unit_mid, Option::WITHIN, 1, P30),
+    opt("mxm_unit_dense", &Context::mxm_unit_dense, Option::WITHIN, 1, P30),
+    opt("mxm_sym_windows", &Context::mxm_sym_windows, Option::WITHIN, 1, 64),
+    opt("mxm_window_groups", &Context::mxm_window_groups, Option::WITHIN, 0, 8, window_group),
+    opt("mxm_xcd_map", &Context::mxm_xcd_map, Option::WITHIN, 0, 1),
+    opt("mxm_checksum_pass", &Context::mxm_checksum_pass, Option::WITHIN, 0, 1),
+    opt("mxm_bitmap_pool_mb", &Context::mxm_bitmap_pool_mb),
+    opt("mxm_bitmap_min_cnt", &Context::mxm_bitmap_min_cnt),
+    opt("mxm_bitmap_pool_cap", &Context::mxm_bitmap_pool_cap),
+    opt("vec_pad_min_bytes", &Context::vec_pad_min_bytes),
+    opt("hub_min_len", &Context::hub_min_len, Option::CLAMP, 0, P30),
+    opt("fill_absent", &Context::fill_absent, Option::WITHIN, 0, 1),
+    opt("rows_tile", &Context::rows_tile, Option::WITHIN, 0, 2),
+    opt("lazy_tagged", &Context::lazy_tagged, Option::WITHIN, 0, 1),
+    opt("ctile_pack", &Context::ctile_pack, Option::WITHIN, 0, 2),
+    opt("strip_slot16", &Context::strip_slot16, Option::WITHIN, 0, 1),
+    opt("rtile_pack", &Context::rtile_pack, Option::WITHIN, 0, 1),
+    opt("cold_in_rows", &Context::cold_in_rows, Option::CLAMP, 0, P30),
+    opt("stream_nt_min_nnz", &Context::stream_nt_min_nnz, Option::CLAMP, 0, MAX64),
+    opt("bool_probe", &Context::bool_probe, Option::WITHIN, 0, 16),
+    opt("rtile_rows", &Context::rtile_rows, Option::ONE_OF, 8192, 16384),
+    opt("rtile_entries", &Context::rtile_entries, Option::WITHIN, 256, 1 << 24),
+    opt("rows_head", &Context::rows_head, Option::WITHIN, 0, 1),
+    opt("rows_head_min_groups", &Context::rows_head_min_groups, Option::CLAMP, 0, MAX64),
+    opt("push_small", &Context::push_small, Option::WITHIN, 0, 1),
+    opt("value_dict", &Context::value_dict, Option::WITHIN, 0, 1),
+    opt("order_mode", &Context::order_mode, Option::WITHIN, 0, 1),
+    opt("order_min_nnz", &Context::order_min_nnz, Option::CLAMP, 0, MAX64),
+    opt("alloc_cache", &Context::alloc_cache, Option::ANY, 0, 0, release_cache_when_off),
+};
+constexpr size_t N_OPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
+int64_t option_initial[N_OPTIONS];  // every option as GrB_init left it: the compiled default, or the environment's override
+
+const Option *option_find(const char *name)
+{
+    for (const Option &o : OPTIONS)
+        if (!strcmp(o.name, name)) return &o;
+    return nullptr;
+}
+int64_t option_load(const Option &o) { return o.i ? (int64_t)(ctx().*o.i) : ctx().*o.l; }
+GrB_Info option_store(const Option &o, int64_t v)
+{
+    if (o.rule == Option::WITHIN && (v < o.lo || v > o.hi)) return GrB_INVALID_VALUE;
+    if (o.rule == Option::ONE_OF && v != o.lo && v != o.hi) return GrB_INVALID_VALUE;
+    if (o.rule == Option::CLAMP) v = std::max(o.lo, std::min(v, o.hi));
+    if (o.hook && !o.hook(v)) return GrB_INVALID_VALUE;
+    if (o.i) ctx().*o.i = (int)v;
+    else ctx().*o.l = v;
+    return GrB_SUCCESS;
+}
+}  // namespace
+
 }  // namespace grb
 
 using namespace grb;
@@ -254,8 +359,6 @@ extern "C" GrB_Info GrB_init(GrB_Mode mode)
     }
     (void)hipGetLastError();
     if (hipEventCreate(&c.ev0) != hipSuccess || hipEventCreate(&c.ev1) != hipSuccess) return GrB_PANIC;
-    if (hipStreamCreateWithFlags(&c.aux_stream, hipStreamNonBlocking) != hipSuccess) c.aux_stream = nullptr;  // (no second stream: the kernels run one after another)
-    if (hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming) != hipSuccess) return GrB_PANIC;
     // The HIP runtime loads a translation unit's code object at the first launch of one of its kernels: several ms for the
     // SpMV unit with its template instantiations -- paid by whichever product came first (it showed up as 8 of the 12.7 ms of
     // the first GrB_mxv of the scale-24 bench).  Load them here, once per process (GRB_PRELOAD=0: on demand, as before).
@@ -269,25 +372,18 @@ extern "C" GrB_Info GrB_init(GrB_Mode mode)
         preload_stage();  // (the page-locked blocks of h2d / d2h: not inside the first matrix's layout build)
     }
     if (const char *e = getenv("GRB_DEBUG_FLAGS")) c.debug_flags = atoi(e) & DEBUG_FLAGS_MASK;
-    // tuning knobs from the environment go through the same validation as GrX_option_set (an invalid value is ignored)
-    static const struct { const char *env, *opt; } knobs[] = {
-        {"GRB_PULL_IPT", "pull_ipt"}, {"GRB_MXV_OVERLAP", "mxv_overlap"}, {"GRB_STRIP_WGS", "strip_wgs"}, {"GRB_HOT_MIN_COLS", "hot_min_cols"}, {"GRB_HOT_K", "hot_k"}, {"GRB_PUSH_MODE", "push_mode"},
-        {"GRB_ALLOC_CACHE", "alloc_cache"}, {"GRB_SHORT_KERNEL", "short_kernel"},
-        {"GRB_LAZY_LAYOUT", "lazy_layout"}, {"GRB_MXM_HEAVY_KERNEL", "mxm_heavy_kernel"}, {"GRB_DROP_HOT_COLS", "drop_hot_cols"},
-        {"GRB_MXM_UNIT_MIN_FLOPS", "mxm_unit_min_flops"}, {"GRB_MXM_UNIT_MIN_PER_WINDOW", "mxm_unit_min_per_window"},
-        {"GRB_MXM_UNIT_SMALL", "mxm_unit_small"}, {"GRB_MXM_UNIT_DENSE", "mxm_unit_dense"}, {"GRB_MXM_UNIT_MID", "mxm_unit_mid"},
-        {"GRB_MXM_BITMAP_POOL_MB", "mxm_bitmap_pool_mb"}, {"GRB_MXM_BITMAP_MIN_CNT", "mxm_bitmap_min_cnt"},
-        {"GRB_LONG_KERNEL", "long_kernel"}, {"GRB_LONG_CLASSES", "long_classes"}, {"GRB_SPLIT_MIN_LEN", "split_min_len"},
-        {"GRB_LONG_SUB", "long_sub"}, {"GRB_LONG_SUB_MIN_LEN", "long_sub_min_len"}, {"GRB_LEAN_MIN_NNZ", "lean_min_nnz"},
-        {"GRB_MXM_MASK_MODE", "mxm_mask_mode"}, {"GRB_MAT_WRITE_KERNEL", "mat_write_kernel"}, {"GRB_MXM_SYM_WINDOWS", "mxm_sym_windows"}, {"GRB_MXM_WINDOW_GROUPS", "mxm_window_groups"}, {"GRB_MXM_CHECKSUM_PASS", "mxm_checksum_pass"}, {"GRB_MXM_XCD_MAP", "mxm_xcd_map"},
-        {"GRB_ORDER_MODE", "order_mode"}, {"GRB_ORDER_MIN_NNZ", "order_min_nnz"}, {"GRB_VALUE_DICT", "value_dict"}, {"GRB_HUB_MIN_LEN", "hub_min_len"}, {"GRB_FILL_ABSENT", "fill_absent"},
-        {"GRB_PUSH_SMALL", "push_small"}, {"GRB_ROWS_HEAD", "rows_head"}, {"GRB_ROWS_TILE", "rows_tile"}, {"GRB_COLD_IN_ROWS", "cold_in_rows"}, {"GRB_RTILE_PACK", "rtile_pack"}, {"GRB_STRIP_SLOT16", "strip_slot16"}, {"GRB_CTILE_PACK", "ctile_pack"}, {"GRB_LAZY_TAGGED", "lazy_tagged"}, {"GRB_BOOL_PROBE", "bool_probe"}, {"GRB_STREAM_NT_MIN_NNZ", "stream_nt_min_nnz"}, {"GRB_RTILE_ROWS", "rtile_rows"}, {"GRB_RTILE_ENTRIES", "rtile_entries"}, {"GRB_ROWS_HEAD_MIN_GROUPS", "rows_head_min_groups"},
-    };
-    c.initialized = true;  // (alloc_cache = 0 releases the block cache: only once the context is complete)
-    for (const auto &k : knobs)
-        if (const char *e = getenv(k.env))
-            if (GrX_option_set(k.opt, atoll(e)) != GrB_SUCCESS)
-                fprintf(stderr, "libgrb_mi355x: %s=%s rejected (not a valid value of option \"%s\"): the default stays\n", k.env, e, k.opt);
+    c.initialized = true;  // (an option may release the block cache: only once the context is complete)
+    // every option from the environment, as GRB_<NAME in upper case>, through the validation of GrX_option_set (an invalid value is ignored);
+    // GRB_DEBUG_FLAGS was read above, where bits the build does not know are dropped instead of rejected
+    for (size_t k = 0; k < N_OPTIONS; k++) {
+        const Option &o = OPTIONS[k];
+        std::string env = "GRB_";
+        for (const char *p = o.name; *p; p++) env += (char)toupper((unsigned char)*p);
+        const char *e = o.i == &Context::debug_flags ? nullptr : getenv(env.c_str());
+        if (e && option_store(o, atoll(e)) != GrB_SUCCESS)
+            fprintf(stderr, "libgrb_mi355x: %s=%s rejected (not a valid value of option \"%s\"): the default stays\n", env.c_str(), e, o.name);
+        option_initial[k] = option_load(o);  // (what GrX_options_reset returns to)
+    }
     return GrB_SUCCESS;
 }
 
@@ -321,11 +417,6 @@ extern "C" GrB_Info GrB_finalize(void)
     if (c.ev0) (void)hipEventDestroy(c.ev0);
     if (c.ev1) (void)hipEventDestroy(c.ev1);
     c.ev0 = c.ev1 = nullptr;
-    if (c.ev_fork) (void)hipEventDestroy(c.ev_fork);
-    if (c.ev_join) (void)hipEventDestroy(c.ev_join);
-    c.ev_fork = c.ev_join = nullptr;
-    if (c.aux_stream) { (void)hipStreamSynchronize(c.aux_stream); (void)hipStreamDestroy(c.aux_stream); }
-    c.aux_stream = nullptr;
     c.initialized = false;
     return GrB_SUCCESS;
 }
@@ -408,128 +499,24 @@ extern "C" GrB_Info GrX_last_stats(GrX_Stats *stats)
 extern "C" GrB_Info GrX_option_set(const char *name, int64_t value)
 {
     if (!name) return GrB_NULL_POINTER;
-    Context &c = ctx();
-    const std::string n(name);
-    if (n == "debug_flags") {
-        if ((int)value & ~DEBUG_FLAGS_MASK) return GrB_INVALID_VALUE;  // kernel ablation switches exist in -DGRB_ABLATE builds only
-        c.debug_flags = (int)value;
-    }
-    else if (n == "pull_ipt") c.tune_pull_ipt = (int)value;
-    else if (n == "mxv_overlap") c.mxv_overlap = value ? 1 : 0;
-    else if (n == "strip_wgs") c.strip_wgs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 4096));
-    else if (n == "hot_min_cols") c.hot_min_cols = value;
-    else if (n == "hot_k") c.hot_k = value;
-    else if (n == "push_mode") c.push_mode = (int)value;
-    else if (n == "split_min_nnz") c.split_min_nnz = value;
-    else if (n == "split_min_len") c.split_min_len = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
-    else if (n == "short_kernel") {
-        // (2 = sliced ELLPACK, 3 = persistent row groups with an LDS head, 4 = a lane per row: measured slower in rounds 1-2, removed)
-        if (value < 0 || value > 6 || value == 2 || value == 3 || value == 4) return GrB_INVALID_VALUE;
-        c.short_kernel = (int)value;
-    }
-    else if (n == "lazy_layout") c.lazy_layout = (int)value;
-    else if (n == "lazy_min_nnz") c.lazy_min_nnz = value;
-    else if (n == "lean_min_nnz") c.lean_min_nnz = value < 0 ? 0 : value;
-    else if (n == "long_kernel") c.long_kernel = (int)value;
-    else if (n == "long_classes") c.long_classes = (value == 16 || value == 32 || value == 64) ? (int)value : 8;
-    else if (n == "long_sub") c.long_sub = (int)std::max<int64_t>(0, std::min<int64_t>(value, 16));
-    else if (n == "long_sub_min_len") c.long_sub_min_len = (int)value;
-    else if (n == "mxm_mask_mode") c.mxm_mask_mode = (int)value;
-    else if (n == "mat_write_kernel") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.mat_write_kernel = (int)value;
-    }
-    else if (n == "mxm_heavy_kernel") c.mxm_heavy_kernel = (int)value;
-    else if (n == "drop_hot_cols") c.drop_hot_cols = (int)value;
-    else if (n == "mxm_unit_min_flops") c.mxm_unit_min_flops = value;
-    else if (n == "mxm_unit_min_per_window") c.mxm_unit_min_per_window = value;
-    else if (n == "mxm_masked_units_min_flops") c.mxm_masked_units_min_flops = value;
-    else if (n == "mxm_unit_small" || n == "mxm_unit_dense" || n == "mxm_unit_mid") {  // class limits of the SpGEMM units: entry counts
-        if (value < 1 || value > (1 << 30)) return GrB_INVALID_VALUE;
-        (n == "mxm_unit_small" ? c.mxm_unit_small : n == "mxm_unit_dense" ? c.mxm_unit_dense : c.mxm_unit_mid) = (int)value;
-    }
-    else if (n == "mxm_sym_windows") {
-        if (value < 1 || value > 64) return GrB_INVALID_VALUE;
-        c.mxm_sym_windows = value;
-    }
-    else if (n == "mxm_window_groups") {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return GrB_INVALID_VALUE;
-        c.mxm_window_groups = value;
-    }
-    else if (n == "mxm_xcd_map") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.mxm_xcd_map = (int)value;
-    }
-    else if (n == "mxm_checksum_pass") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.mxm_checksum_pass = (int)value;
-    }
-    else if (n == "mxm_bitmap_pool_mb") c.mxm_bitmap_pool_mb = value;
-    else if (n == "mxm_bitmap_min_cnt") c.mxm_bitmap_min_cnt = (int)value;
-    else if (n == "mxm_bitmap_pool_cap") c.mxm_bitmap_pool_cap = value;
-    else if (n == "vec_pad_min_bytes") c.vec_pad_min_bytes = value;
-    else if (n == "hub_min_len") c.hub_min_len = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
-    else if (n == "fill_absent") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.fill_absent = (int)value;
-    }
-    else if (n == "rows_tile") {
-        if (value != 0 && value != 1 && value != 2) return GrB_INVALID_VALUE;
-        c.rows_tile = (int)value;
-    }
-    else if (n == "lazy_tagged") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.lazy_tagged = (int)value;
-    }
-    else if (n == "ctile_pack") {
-        if (value < 0 || value > 2) return GrB_INVALID_VALUE;
-        c.ctile_pack = (int)value;
-    }
-    else if (n == "strip_slot16") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.strip_slot16 = (int)value;
-    }
-    else if (n == "rtile_pack") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.rtile_pack = (int)value;
-    }
-    else if (n == "cold_in_rows") c.cold_in_rows = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
-    else if (n == "stream_nt_min_nnz") c.stream_nt_min_nnz = value < 0 ? 0 : value;
-    else if (n == "bool_probe") {
-        if (value < 0 || value > 16) return GrB_INVALID_VALUE;
-        c.bool_probe = (int)value;
-    }
-    else if (n == "rtile_rows") {
-        if (value != 8192 && value != 16384) return GrB_INVALID_VALUE;
-        c.rtile_rows = (int)value;
-    }
-    else if (n == "rtile_entries") {
-        if (value < 256 || value > (1 << 24)) return GrB_INVALID_VALUE;
-        c.rtile_entries = value;
-    }
-    else if (n == "rows_head") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.rows_head = (int)value;
-    }
-    else if (n == "rows_head_min_groups") c.rows_head_min_groups = value < 0 ? 0 : value;
-    else if (n == "push_small") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.push_small = (int)value;
-    }
-    else if (n == "value_dict") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.value_dict = (int)value;
-    }
-    else if (n == "order_mode") {
-        if (value != 0 && value != 1) return GrB_INVALID_VALUE;
-        c.order_mode = (int)value;
-    }
-    else if (n == "order_min_nnz") c.order_min_nnz = value < 0 ? 0 : value;
-    else if (n == "alloc_cache") {
-        if (!value) dev_cache_release();
-        c.alloc_cache = (int)value;
-    }
-    else return GrB_INVALID_VALUE;
+    const Option *o = option_find(name);
+    return o ? option_store(*o, value) : GrB_INVALID_VALUE;
+}
+
+extern "C" GrB_Info GrX_option_get(const char *name, int64_t *value)
+{
+    if (!name || !value) return GrB_NULL_POINTER;
+    const Option *o = option_find(name);
+    if (!o) return GrB_INVALID_VALUE;
+    *value = option_load(*o);
+    return GrB_SUCCESS;
+}
+
+extern "C" GrB_Info GrX_options_reset(void)
+{
+    if (!ctx().initialized) return GrB_PANIC;
+    for (size_t k = 0; k < N_OPTIONS; k++)
+        if (option_store(OPTIONS[k], option_initial[k]) != GrB_SUCCESS) return GrB_PANIC;  // (a stored value is a valid value)
     return GrB_SUCCESS;
 }
 

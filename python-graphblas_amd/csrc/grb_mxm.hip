@@ -695,25 +695,6 @@ constexpr int MU_POOLS = 1024;  // sub-pools of the bitmap pool
 #define GRB_MU_SMALL 512
 #endif
 constexpr int MU_SMALL = GRB_MU_SMALL;  // entries of a unit a single wavefront accumulates
-// Units per wavefront of the numeric one-wavefront class (round 6, VERDICT r03-r05 "two independent units interleaved per wavefront").
-// A unit is a chain of dependent round trips -- its record, the entries of A, their window offsets and row pointers of B, the
-// bitmap, then the products -- and LDS holds the workgroups per CU at four, i.e. four chains per SIMD.  With GRB_MU_UPW = 2 a
-// wavefront owns two consecutive units of the class list (neighbouring windows of one row, as a rule): both records and both
-// offset chains are requested BEFORE the first unit's bitmap and products are touched, so the second unit's chain travels
-// under the first unit's work; the units then run one after the other in the same LDS (no more LDS, +14 registers).
-// MEASURED (profiles/r06/mxm_units_per_wavefront.txt, INT64 A (+.x) A, ms per product, UPW = 1 / 2 / 3): scale 20 (single windows)
-// 130.0 / 134.2 / 133.3; scale 22 (window pairs) 1292.8 / 1270.7 / 1265.4, run-to-run noise +-0.5 %.  The offset chain is not what a unit
-// waits for (round 3 found the same for the symbolic units); a unit's TRIPS are, and two units' trips in flight at once need two
-// bitmaps and two accumulator sets -- the LDS that already holds the class at four workgroups per CU.  Default: 1 (2 from window
-// groups on would buy 1.7 % at scale 22 and cost 3 % wherever single windows run).
-#ifndef GRB_MU_UPW
-#define GRB_MU_UPW 1
-#endif
-#ifndef GRB_MU_PIPE
-#define GRB_MU_PIPE 0  // bit 0: the trips of a batch of the SEARCH dealing (one-wavefront numeric class) are software-pipelined (round 6), bit 1: the trips
-                       // of a segment of the RANKED dealing (every other class); 0: load, wait, apply per trip (rounds 2-5).  See the measurement at the loops.
-#endif
-constexpr int mu_units_per_wave(int mode, int wpu) { return (mode == 1 && wpu == 1) ? GRB_MU_UPW : 1; }
 
 __device__ __forceinline__ void mw_sync()
 {
@@ -762,43 +743,16 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
     const int uib = WPU == 1 ? wave : 0, sub = WPU == 1 ? 0 : wave;  // unit inside the workgroup, wavefront inside the unit
     const int nwin = a.n_win;                   // (windows: the tables' unit)
     const int ngroups_w = (nwin + F - 1) / F;   // (groups of F windows: the units' unit)
-    constexpr int UPW = mu_units_per_wave(MODE, WPU);  // units this wavefront owns (numeric one-wavefront class: GRB_MU_UPW)
+    constexpr int UPW = 1;  // units a wavefront owns: one (two and three were measured, docs/HISTORY.md)
     const int64_t unit = (xcd_block(a) * UPB + uib) * UPW;
     int64_t ridx = 0, row, out = 0, pbeg, pend;
     int w, w_end = 0, bslot = -1, mcnt = 0;
     constexpr int NB = 2;  // batches of entries of A a wavefront keeps (range of B inside the window) from pass A for pass B
     UnitRec urec[UPW];
-    int pf_len[UPW][NB];     // (UPW > 1: the ranges of B of every owned unit's first NB batches, requested up front)
-    int64_t pf_qb[UPW][NB];
     if constexpr (NUMERIC) {  // a unit of the class list
         if (unit >= nunits) return;  // (uniform over the unit's threads)
 #pragma unroll
-        for (int k = 0; k < UPW; k++) urec[k] = units[unit + k < nunits ? unit + k : nunits - 1];  // (past the list: the last unit again, never run)
-        if constexpr (UPW > 1) {
-            // both offset chains, stage by stage: all entries of A first, then everything that depends on them -- the loads of the
-            // second unit leave with the first unit's instead of behind its products
-            int pk[UPW][NB];
-            bool pok[UPW][NB];
-#pragma unroll
-            for (int k = 0; k < UPW; k++)
-#pragma unroll
-                for (int b = 0; b < NB; b++) {
-                    const int64_t pe = urec[k].pbeg + urec[k].plen, pp = urec[k].pbeg + (int64_t)b * 64 + (int64_t)lane;
-                    pok[k][b] = pp < pe;
-                    pk[k][b] = a.Aj[pok[k][b] ? pp : pe - 1];
-                }
-#pragma unroll
-            for (int k = 0; k < UPW; k++)
-#pragma unroll
-                for (int b = 0; b < NB; b++) {
-                    const int wk = urec[k].w;
-                    const int fs = a.n_win - wk * F < F ? a.n_win - wk * F : F;
-                    const int32_t *o = a.woff + (int64_t)pk[k][b] * (a.n_win + 1) + wk * F;
-                    const int o0 = o[0], o1 = o[fs];
-                    pf_qb[k][b] = a.Bp[pk[k][b]] + o0;
-                    pf_len[k][b] = pok[k][b] ? o1 - o0 : 0;
-                }
-        }
+        for (int k = 0; k < UPW; k++) urec[k] = units[unit + k < nunits ? unit + k : nunits - 1];
         const UnitRec &r = urec[0];
         row = r.row;
         w = r.w;
@@ -843,24 +797,11 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
     }
     const int tiu = sub * 64 + lane;  // thread inside the unit
     unsigned long long csum_mine = 0;  // (streamed product: the values this thread stores)
-    // (the units this wavefront owns, one instance of the body per unit -- `uk` is a compile-time constant: a run-time loop over them was
-    //  left un-unrolled by the compiler, and the prefetched ranges, indexed by `uk`, went to scratch memory; UPW = 1 everywhere but in
-    //  the numeric one-wavefront class)
+    // (the unit body is a generic lambda over the unit's number and the record arrives through `urec`: the shape the shipped code was compiled
+    //  from when a wavefront could own several units.  Written flat -- a plain record, no lambda -- k_spgemm_unit compiles to other code in
+    //  dozens of instantiations, some with more registers, so the shape stays)
     auto run_unit = [&](auto uk_c) {
     constexpr int uk = decltype(uk_c)::value;
-    if constexpr (UPW > 1) {
-        if (uk > 0) {
-            if (unit + uk >= nunits) return;  // (uniform over the wavefront)
-            usync();  // (the next unit clears / loads the bitmap and the accumulators the last one wrote its columns from)
-            const UnitRec &r = urec[uk];
-            row = r.row;
-            w = r.w;
-            out = r.out;
-            pbeg = r.pbeg;
-            pend = pbeg + r.plen;
-            bslot = r.aux;
-        }
-    }
     for (;;) {  // (the windows of a symbolic unit; numeric and masked units: once)
     const int c0 = w * WIN;
     const int fspan = nwin - w * F < F ? nwin - w * F : F;  // windows of the group that exist (the last group of a row may be short)
@@ -878,16 +819,8 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
         qb = a.Bp[k] + o0;
         len = ok ? o1 - o0 : 0;
     };
-    if constexpr (UPW > 1) {
 #pragma unroll
-        for (int b = 0; b < NB; b++) {
-            c_len[b] = pf_len[uk][b];
-            c_qb[b] = pf_qb[uk][b];
-        }
-    } else {
-#pragma unroll
-        for (int b = 0; b < NB; b++) fetch(pbeg + sub + (int64_t)b * 64 * WPU + (int64_t)lane * WPU, c_len[b], c_qb[b]);
-    }
+    for (int b = 0; b < NB; b++) fetch(pbeg + sub + (int64_t)b * 64 * WPU + (int64_t)lane * WPU, c_len[b], c_qb[b]);
     if (bslot >= 0) {  // (numeric pass: the symbolic pass kept the unit's bitmap)
         for (int k = tiu; k < WORDS; k += 64 * WPU) bits[k] = a.bm_pool[(int64_t)bslot * FWORDS + k];  // (F consecutive window bitmaps)
     } else {
@@ -925,48 +858,6 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
                 mw_sync();
                 // ILP products per lane and TRIP: their searches interleave and their loads are issued back to back -- every product number
                 // is clamped into the batch instead of being guarded by a branch (a guarded load is waited for inside its branch).
-                // Round 6 (GRB_MU_PIPE): the trips of a batch are SOFTWARE-PIPELINED -- the loads of trip k + 1 are issued before the
-                // products of trip k go to LDS, through two register sets with static roles (no copies: a copied register waits for its
-                // load), and only trips that exist are ever requested (the loop runs while two more trips follow; the last one or two
-                // are peeled).  A unit's wavefront used to wait one global round trip per trip with nothing else of its own in flight.
-                if constexpr ((GRB_MU_PIPE & 1) != 0) {
-                using D = decltype(load((const int32_t *)nullptr, 0u, 0));
-                constexpr int TRIP = 64 * ILP;
-                auto fetch_trip = [&](int base, D (&d)[ILP]) {
-#pragma unroll
-                    for (int u = 0; u < ILP; u++) {
-                        const int tt = base + lane + 64 * u;
-                        const int t = tt < total ? tt : total - 1;
-                        int lo = 0;  // the last entry whose first product number is <= t (scan[0] = 0 <= t): six steps, three VALU each
-#pragma unroll
-                        for (int st = 32; st > 0; st >>= 1)
-                            if (scan[lo + st] <= t) lo += st;
-                        d[u] = load(a.Bj + sqb[lo], (unsigned)t, lo);
-                    }
-                };
-                auto apply_trip = [&](int base, const D (&d)[ILP]) {
-#pragma unroll
-                    for (int u = 0; u < ILP; u++)
-                        if (base + lane + 64 * u < total) apply(d[u]);
-                };
-                D da[ILP], db[ILP];
-                int base = 0;
-                fetch_trip(0, da);
-                while (base + 2 * TRIP < total) {  // (uniform: two more trips follow the one in `da`)
-                    fetch_trip(base + TRIP, db);
-                    apply_trip(base, da);
-                    fetch_trip(base + 2 * TRIP, da);
-                    apply_trip(base + TRIP, db);
-                    base += 2 * TRIP;
-                }
-                if (base + TRIP < total) {
-                    fetch_trip(base + TRIP, db);
-                    apply_trip(base, da);
-                    apply_trip(base + TRIP, db);
-                } else {
-                    apply_trip(base, da);
-                }
-                } else {
                 for (int t0 = lane; t0 < total; t0 += 64 * ILP) {  // (rounds 2-5: load, wait, apply per trip)
                     decltype(load((const int32_t *)nullptr, 0u, 0)) d[ILP];
 #pragma unroll
@@ -981,7 +872,6 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
 #pragma unroll
                     for (int u = 0; u < ILP; u++)
                         if (t0 + 64 * u < total) apply(d[u]);
-                }
                 }
                 mw_sync();
                 return;
@@ -1024,42 +914,6 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
                 const short *rpb = recb;
                 unsigned t = (unsigned)(seg0 + lane);
                 const unsigned t_last = (unsigned)(total - 1);
-                // (round 6, GRB_MU_PIPE: the trips of a segment software-pipelined as in the search dealing above -- the loads of trip k + 1
-                //  leave before the products of trip k go to LDS; two register sets with static roles; only trips that exist are requested)
-                if constexpr ((GRB_MU_PIPE & 2) != 0) {
-                using D = decltype(load((const int32_t *)nullptr, 0u, 0));
-                auto fetch_grp = [&](int g0, D (&d)[ILP]) {
-#pragma unroll
-                    for (int u = 0; u < ILP; u++) {
-                        const int rank = (int)rpb[g0 + u] + __popcll(rpm[g0 + u] & lane_le);
-                        const unsigned tt = t + 64u * (unsigned)(g0 + u);
-                        const unsigned tu = tt < t_last ? tt : t_last;
-                        d[u] = load(cptr[rank], tu, rank);
-                    }
-                };
-                auto apply_grp = [&](int g0, const D (&d)[ILP]) {
-#pragma unroll
-                    for (int u = 0; u < ILP; u++)
-                        if (t + 64u * (unsigned)(g0 + u) <= t_last) apply(d[u]);
-                };
-                D da[ILP], db[ILP];
-                int g0 = 0;
-                fetch_grp(0, da);
-                while (g0 + 2 * ILP < g_n) {  // (uniform: two more trips follow the one in `da`)
-                    fetch_grp(g0 + ILP, db);
-                    apply_grp(g0, da);
-                    fetch_grp(g0 + 2 * ILP, da);
-                    apply_grp(g0 + ILP, db);
-                    g0 += 2 * ILP;
-                }
-                if (g0 + ILP < g_n) {
-                    fetch_grp(g0 + ILP, db);
-                    apply_grp(g0, da);
-                    apply_grp(g0 + ILP, db);
-                } else {
-                    apply_grp(g0, da);
-                }
-                } else {
                 for (int g0 = 0; g0 < g_n; g0 += ILP, rpm += ILP, rpb += ILP, t += 64 * ILP) {  // (rounds 3-5: load, wait, apply per trip)
                     decltype(load((const int32_t *)nullptr, 0u, 0)) d[ILP];
 #pragma unroll
@@ -1071,7 +925,6 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
 #pragma unroll
                     for (int u = 0; u < ILP; u++)
                         if (t + 64u * u <= t_last) apply(d[u]);
-                }
                 }
                 mw_sync();
             }
@@ -1282,10 +1135,6 @@ __global__ __launch_bounds__(64 * (WPU > 4 ? WPU : 4), mu_min_waves(MODE, WPU, C
     }  // for (;;)
     };  // run_unit
     run_unit(std::integral_constant<int, 0>{});
-    if constexpr (UPW > 1) run_unit(std::integral_constant<int, 1>{});
-    if constexpr (UPW > 2) run_unit(std::integral_constant<int, 2>{});
-    if constexpr (UPW > 3) run_unit(std::integral_constant<int, 3>{});
-    static_assert(UPW >= 1 && UPW <= 4, "one to four units per wavefront");
     if constexpr (NUMERIC && !MASKED) checksum_commit(a, csum_mine);
 }
 
@@ -1994,7 +1843,7 @@ static void launch_unit_classes(MxmArgs &a, const uint32_t *rows, int64_t nrows,
     auto compact_classes = [&](int c0, auto f_c) {
         constexpr int F = decltype(f_c)::value;
         per_class(c0, [&](const UnitRec *u, int64_t nu) {
-            hipLaunchKernelGGL((k_spgemm_unit<T, MODE, 1, MU_SMALL, F>), dim3(grid8(ceil_div(nu, (int64_t)4 * mu_units_per_wave(MODE, 1)))), dim3(256), 0, ctx().stream, a, rows, 0, 0, u, nu);
+            hipLaunchKernelGGL((k_spgemm_unit<T, MODE, 1, MU_SMALL, F>), dim3(grid8(ceil_div(nu, (int64_t)4))), dim3(256), 0, ctx().stream, a, rows, 0, 0, u, nu);
         });
         per_class(c0 + 1, [&](const UnitRec *u, int64_t nu) {
             hipLaunchKernelGGL((k_spgemm_unit<T, MODE, 4, 1024, F>), dim3(grid8(nu)), dim3(256), 0, ctx().stream, a, rows, 0, 0, u, nu);

@@ -180,13 +180,6 @@ __device__ __forceinline__ bool write_rule_row(const PullArgs &a, int64_t row, b
 
 // Ablation / diagnostic switches (PullArgs::dbg, option "debug_flags") exist in the kernels of an ABLATION build only
 // (-DGRB_ABLATE: scripts/variants_ab.sh, the emulator build of the CPU test tier); the shipped library compiles them out.
-// build-time experiment (scripts/variants_ab.sh, results are WRONG): -DGRB_GATHER_HALF gathers operand values from half the index --
-// the footprint a 16-bit image of the operand would have, with the same number of gathers
-#ifdef GRB_GATHER_HALF
-#define GRB_GATHER_IDX(c) ((c) >> 1)
-#else
-#define GRB_GATHER_IDX(c) (c)
-#endif
 #ifdef GRB_ABLATE
 #define GRB_DBG(a, bits) ((a).dbg & (bits))
 #define EARLY_EXIT(level) do { if (((a.dbg >> 8) & 15) == (level)) return; } while (0)

@@ -29,23 +29,12 @@ constexpr int CT_SLOTS = GRB_CT_SLOTS;  // long rows per tile
 constexpr int CT_PACK_SLOTS = 8192, CT_PACK_COLBITS = 19;  // (round 6, packed words: slot << 19 | column - range base; 13 + 19 bits)
 constexpr int CT_BLOCK = GRB_CT_BLOCK;
 constexpr int CT_EPL = 4;
-#ifndef GRB_CT_UB
-#define GRB_CT_UB 1  // units of 4 entries a thread has under way per pass.  Round 5 measured 1 / 2 / 4 / 8: k_mxv_ctile 131 / ~137 / 143 / 270 us per
-                     // masked scale-24 call (profiles/r05/ctile_units_per_pass.txt) -- as in round 4, more gathers in flight per thread make this
-                     // kernel slower: it is bound by the L1 miss path of its gathers, not by the round trips of a pass
-#endif
 #ifndef GRB_CT_WGS_PER_CU
 #define GRB_CT_WGS_PER_CU 2  // (round 4: 68 KiB of LDS per 1024-thread workgroup with 16 Ki slots.  Round 3, 4 Ki slots sorted by row: (24 KiB of LDS per 512-thread workgroup for 4-byte accumulators: 32 wavefronts per CU.  Measured on the headline
                              //  call, ms: 8192 rows x 256 threads x 3 per CU 0.716-0.735; 8192 x 1024 x 2 0.677; 4096 x 256 x 6 0.671-0.676;
                              //  4096 x 512 x 4 0.674; 2048 x 256 x 8 0.691; 1024 x 256 x 8 0.718 -- profiles/r03/ctile_variants*.txt)
 #endif
 constexpr int CT_WGS_PER_CU = GRB_CT_WGS_PER_CU;
-#ifndef GRB_CT_PIPE
-#define GRB_CT_PIPE 0  // 1: the software-pipelined pass loop of round 6 for the common call (see k_mxv_ctile); 0: the pass-at-a-time loop of rounds 3-5.
-                       // MEASURED (profiles/r06/ctile_experiments.txt): pipelined 151.4 us (clamped re-reads behind the tile) / 151.6 us (buffer loads that
-                       // move nothing behind the tile; waits vmcnt(5..8), 64 registers, no spills) against 125.6 us pass-at-a-time -- like the 2 / 4 / 8
-                       // units per pass of round 5 (131 -> 137 / 143 / 270): MORE gathers in flight per CU make this kernel slower.  Off.
-#endif
 #ifndef GRB_CT_ABL
 #define GRB_CT_ABL 0  // build-time ablation (results WRONG): 1 no operand gathers (the value of the entry stands in), 2 no flush of the tile's accumulators, 4 no LDS atomics
 #endif
@@ -171,95 +160,12 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
         }
         __syncthreads();
         const int64_t u_end = tile.u0 + tile.n_units;
-        // ---- round 6: the common call (a full operand whose values are read, values of the matrix read, a 4- or 8-byte type) walks the
-        //      tile as a SOFTWARE PIPELINE.  The loop below it asks for a pass's entries, waits, asks for their operand values, waits, folds
-        //      -- two memory round trips per pass of 4096 entries with nothing else of the workgroup in flight, four passes per tile (the
-        //      hypothesis: the kernel is bound by that chain; the measurement says otherwise, see GRB_CT_PIPE: built, verified, off).  Here the
-        //      entries of pass j + 2 are requested, then the operand values of pass j + 1, then pass j is folded; the stage registers are
-        //      rings with static indices (the rule of DESIGN 4.1.0: a static number of memory instructions per iteration, predication
-        //      through the address, no register copies), a pass behind the tile's end re-reads the last unit and gathers nothing.
-        bool piped = false;
-        if constexpr (!std::is_same<T, bool>::value && (sizeof(T) == 4 || sizeof(T) == 8) && GRB_CT_PIPE) {
-            piped = a.u_full && need_uval && stage_vals && !packed;  // (uniform over the launch)
-            if (piped) {
-                struct Ent {
-                    uint4 c;
-                    uint2 l;
-                    T v[EPL];
-                };
-                const int n_steps = (int)((tile.n_units + CT_BLOCK - 1) / CT_BLOCK);
-                auto valid_at = [&](int st) { return tile.u0 + (int64_t)st * CT_BLOCK + threadIdx.x < u_end; };
-                // (the tile's streams through buffer descriptors over THIS TILE: a unit behind its end -- the steps that only drain the
-                //  pipeline -- lies beyond them, returns zeros and moves nothing; a clamped re-read of the last unit, the first form of this
-                //  loop, doubled the stream instructions of a four-step tile: 125 -> 151 us)
-                const __amdgpu_buffer_rsrc_t col_rs = make_rsrc(tcol + tile.u0 * EPL, (int64_t)tile.n_units * 16);
-                const __amdgpu_buffer_rsrc_t loc_rs = make_rsrc(tloc + tile.u0 * EPL, (int64_t)tile.n_units * 8);
-                const __amdgpu_buffer_rsrc_t val_rs = make_rsrc(tval + tile.u0 * EPL, (int64_t)tile.n_units * EPL * (int64_t)sizeof(T));
-                auto load_ent = [&](int st) {
-                    Ent r;
-                    const unsigned k = (unsigned)st * (unsigned)CT_BLOCK + threadIdx.x;  // (unit inside the tile; tiles hold far fewer than 2^26 units)
-                    r.c = buf_stream_x4(col_rs, k * 16u, snt);
-                    r.l = buf_stream_x2(loc_rs, k * 8u, snt);
-                    if constexpr (sizeof(T) == 4) {
-                        const uint4 v4 = buf_stream_x4(val_rs, k * 16u, snt);
-                        r.v[0] = __builtin_bit_cast(T, v4.x); r.v[1] = __builtin_bit_cast(T, v4.y);
-                        r.v[2] = __builtin_bit_cast(T, v4.z); r.v[3] = __builtin_bit_cast(T, v4.w);
-                    } else {
-                        const uint4 va = buf_stream_x4(val_rs, k * 32u, snt), vb = buf_stream_x4(val_rs, k * 32u + 16u, snt);
-                        r.v[0] = __builtin_bit_cast(T, (unsigned long long)va.x | ((unsigned long long)va.y << 32));
-                        r.v[1] = __builtin_bit_cast(T, (unsigned long long)va.z | ((unsigned long long)va.w << 32));
-                        r.v[2] = __builtin_bit_cast(T, (unsigned long long)vb.x | ((unsigned long long)vb.y << 32));
-                        r.v[3] = __builtin_bit_cast(T, (unsigned long long)vb.z | ((unsigned long long)vb.w << 32));
-                    }
-                    return r;
-                };
-                // (bit i of the returned mask: entry i is live -- a valid unit, a row the mask admits, not padding)
-                auto gather_ent = [&](const Ent &en, bool valid, T (&xv)[EPL]) -> uint32_t {
-                    const int creg[EPL] = {(int)en.c.x, (int)en.c.y, (int)en.c.z, (int)en.c.w};
-                    const int rk[EPL] = {(int)(en.l.x & 0xffffu), (int)(en.l.x >> 16), (int)(en.l.y & 0xffffu), (int)(en.l.y >> 16)};
-                    uint32_t live = 0u;
-#pragma unroll
-                    for (int i = 0; i < EPL; i++) {
-                        const int cc = valid ? (creg[i] | -(int)((s_off[rk[i] >> 5] >> (rk[i] & 31)) & 1u)) : -1;
-                        live |= (cc >= 0 ? 1u : 0u) << i;
-                        xv[i] = buf_gather<T>(xval_rs, cc >= 0 ? (unsigned)GRB_GATHER_IDX(cc) * (unsigned)sizeof(T) : 0xfffffff8u);
-                    }
-                    return live;
-                };
-                auto fold_ent = [&](const Ent &en, const T (&xv)[EPL], uint32_t live) {
-                    const int rk[EPL] = {(int)(en.l.x & 0xffffu), (int)(en.l.x >> 16), (int)(en.l.y & 0xffffu), (int)(en.l.y >> 16)};
-#pragma unroll
-                    for (int i = 0; i < EPL; i++) {
-                        if (!((live >> i) & 1u)) continue;
-                        const int r = rk[i];
-                        const T prod = apply_binop<T>(mult, en.v[i], xv[i]);
-                        if (monoid == OP_ANY) s_acc[r] = (W)prod;
-                        else lds_combine<W>(&s_acc[r], (W)prod, monoid);
-                        atomicOr(&s_has[r >> 5], 1u << (r & 31));
-                    }
-                };
-                constexpr int RING = 3;
-                Ent eb[RING];
-                T xb[RING][EPL];
-                uint32_t lv[RING];
-                eb[0] = load_ent(0);
-                eb[1] = load_ent(1);
-                lv[0] = gather_ent(eb[0], valid_at(0), xb[0]);
-                for (int jb = 0; jb < n_steps; jb += RING) {
-#pragma unroll
-                    for (int q = 0; q < RING; q++) {
-                        const int j = jb + q;  // (no early exit inside the unrolled body: the ring indices must stay static)
-                        eb[(q + 2) % RING] = load_ent(j + 2);
-                        lv[(q + 1) % RING] = gather_ent(eb[(q + 1) % RING], valid_at(j + 1), xb[(q + 1) % RING]);
-                        if (j < n_steps) fold_ent(eb[q], xb[q], lv[q]);
-                    }
-                }
-            }
-        }
-        // UB units per thread and pass: the entries of all of them requested first, then all their gathers, then the products (a unit behind
-        // the tile's end re-reads the last one and is switched off).  UB = 1 is the shipped form, see GRB_CT_UB.
-        constexpr int UB = GRB_CT_UB;
-        for (int64_t ub0 = tile.u0; !piped && ub0 < u_end; ub0 += (int64_t)CT_BLOCK * UB) {  // (uniform over the workgroup)
+        // UB units of four entries per thread and pass: the entries of all of them requested first, then all their gathers, then the products
+        // (a unit behind the tile's end re-reads the last one and is switched off).  One unit: 2 / 4 / 8 were measured slower (docs/HISTORY.md).
+        // The arrays keep the unit dimension: written without it the compiler lays the pass out differently (k_mxv_ctile<bool, ..> takes
+        // two more registers), and this loop is the hot path of the cold tiles.
+        constexpr int UB = 1;
+        for (int64_t ub0 = tile.u0; ub0 < u_end; ub0 += (int64_t)CT_BLOCK * UB) {  // (uniform over the workgroup)
             const int64_t ub = ub0 + threadIdx.x;
             int creg[UB][EPL], rk[UB][EPL], cc[UB][EPL];
             T vreg[UB][EPL];
@@ -362,7 +268,7 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
 #pragma unroll
                     for (int k = 0; k < UB; k++)
 #pragma unroll
-                        for (int i = 0; i < EPL; i++) xv[k][i] = buf_gather<T>(xval_rs, xp[k][i] ? (unsigned)GRB_GATHER_IDX(cc[k][i]) * (unsigned)sizeof(T) : 0xfffffff8u);
+                        for (int i = 0; i < EPL; i++) xv[k][i] = buf_gather<T>(xval_rs, xp[k][i] ? (unsigned)cc[k][i] * (unsigned)sizeof(T) : 0xfffffff8u);
                 }
             } else {
 #pragma unroll

@@ -224,7 +224,7 @@ __device__ __forceinline__ void rows_group(const PullArgs &a, int64_t g, int lan
             } else {
                 T xg[EPL];
 #pragma unroll
-                for (int i = 0; i < EPL; i++) xg[i] = buf_gather<T>(xval_rs, (xp[i] && cc[i] >= head_n) ? (unsigned)GRB_GATHER_IDX(cc[i]) * (unsigned)sizeof(T) : 0xfffffff8u);
+                for (int i = 0; i < EPL; i++) xg[i] = buf_gather<T>(xval_rs, (xp[i] && cc[i] >= head_n) ? (unsigned)cc[i] * (unsigned)sizeof(T) : 0xfffffff8u);
 #pragma unroll
                 for (int i = 0; i < EPL; i++) {
                     xv[i] = xg[i];

@@ -353,11 +353,11 @@ __global__ __launch_bounds__(HEAD ? TAG_HEAD_BLOCK : ROWS_BLOCK, HEAD ? 8 : 1) v
                         for (int i = 0; i < EPL; i++) xv[i] = (unsigned)cc[i] < (unsigned)HEAD_SLOTS ? hx[i] : xv[i];
                     } else {
 #pragma unroll
-                        for (int i = 0; i < EPL; i++) xv[i] = buf_gather<T>(xval_rs, (unsigned)GRB_GATHER_IDX(cc[i]) * (unsigned)sizeof(T));  // (-1: out of range)
+                        for (int i = 0; i < EPL; i++) xv[i] = buf_gather<T>(xval_rs, (unsigned)cc[i] * (unsigned)sizeof(T));  // (-1: out of range)
                     }
                 } else {
 #pragma unroll
-                    for (int i = 0; i < EPL; i++) xv[i] = buf_gather<T>(xval_rs, xp[i] ? (unsigned)GRB_GATHER_IDX(cc[i]) * (unsigned)sizeof(T) : 0xfffffff8u);
+                    for (int i = 0; i < EPL; i++) xv[i] = buf_gather<T>(xval_rs, xp[i] ? (unsigned)cc[i] * (unsigned)sizeof(T) : 0xfffffff8u);
                 }
             } else {
 #pragma unroll

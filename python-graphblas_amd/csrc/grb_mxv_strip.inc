@@ -372,7 +372,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_strip(const PullArgs a)
             } else {
 #pragma unroll
                 for (int i = 0; i < EPL; i++) {
-                    const T v = buf_gather<T>(xval_rs, (unsigned)GRB_GATHER_IDX(st.cc[i]) * (unsigned)sizeof(T));  // (negative: out of range)
+                    const T v = buf_gather<T>(xval_rs, (unsigned)st.cc[i] * (unsigned)sizeof(T));  // (negative: out of range)
                     if constexpr (sizeof(T) == 8) st.g[i] = __builtin_bit_cast(uint64_t, v);
                     else if constexpr (sizeof(T) == 4) st.g[i] = __builtin_bit_cast(uint32_t, v);
                     else st.g[i] = (uint32_t)__builtin_bit_cast(typename UintOfSize<sizeof(T)>::type, v);
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_mxv_strip(const PullArgs a)
                 } else {
                     T xg[EPL];
 #pragma unroll
-                    for (int i = 0; i < EPL; i++) xg[i] = buf_gather<T>(xval_rs, (xp[i] && st.cc[i] >= 0) ? (unsigned)GRB_GATHER_IDX(st.cc[i]) * (unsigned)sizeof(T) : 0xfffffff8u);
+                    for (int i = 0; i < EPL; i++) xg[i] = buf_gather<T>(xval_rs, (xp[i] && st.cc[i] >= 0) ? (unsigned)st.cc[i] * (unsigned)sizeof(T) : 0xfffffff8u);
 #pragma unroll
                     for (int i = 0; i < EPL; i++) {
                         const T xl = lds_value(st.cc[i]);

@@ -153,6 +153,4 @@ def test_hub_rows_real_values(gb, tname, sr, request):
             # the product of two FP32 numbers rounds once; min / max then pick one of them exactly
             _close(wv, want[has], rtol=RTOL)
     finally:
-        _lib.lib.GrX_option_set(b"split_min_nnz", 1 << 22)
-        _lib.lib.GrX_option_set(b"hot_min_cols", 1 << 20)
-        _lib.lib.GrX_option_set(b"push_mode", 1)
+        assert _lib.lib.GrX_options_reset() == 0

@@ -243,9 +243,7 @@ def test_mxm_unit_kernels_against_row_kernels_at_scale(gb, scale, weighted):
             C = A.mxm(A, sr).new()
             return C, device.last_stats()
         finally:
-            for k, v in dict(mxm_heavy_kernel=1, mxm_unit_small=512, mxm_unit_mid=1024, mxm_unit_dense=4096,
-                             mxm_bitmap_pool_cap=(1 << 31) - 1, mxm_unit_min_flops=1024).items():
-                L.GrX_option_set(k.encode(), v)
+            assert L.GrX_options_reset() == 0
 
     C1, st1 = product()
     C0, st0 = product(mxm_heavy_kernel=0)
@@ -272,13 +270,13 @@ def test_mxm_unit_kernels_against_row_kernels_at_scale(gb, scale, weighted):
             L.GrX_option_set(b"mxm_heavy_kernel", 0)
             M0 = A.mxm(A, sr).new(mask=A.S)
         finally:
-            L.GrX_option_set(b"mxm_heavy_kernel", 1)
+            assert L.GrX_options_reset() == 0
         assert M1.isequal(M0)
         try:
             L.GrX_option_set(b"mxm_mask_mode", 0)  # (the full product, then the write rule)
             M2 = A.mxm(A, sr).new(mask=A.S)
         finally:
-            L.GrX_option_set(b"mxm_mask_mode", 1)
+            assert L.GrX_options_reset() == 0
         assert M1.isequal(M2) and M1.nvals > n
 
 

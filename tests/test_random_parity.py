@@ -17,7 +17,7 @@ TYPES = ["INT64", "FP32", "BOOL", "FP64", "INT8", "UINT16", "INT32"]
 import os
 
 DEFAULT_SHORT_KERNEL = int(os.environ.get("GRB_SHORT_KERNEL", "6"))
-DEFAULT_LONG_KERNEL = int(os.environ.get("GRB_LONG_KERNEL", "5"))  # what tests restore after forcing a long-row kernel
+DEFAULT_LONG_KERNEL = int(os.environ.get("GRB_LONG_KERNEL", "5"))  # (the "by size" choices some seeds force next to the explicit kernels)
 
 
 @pytest.fixture(params=DEVICES)
@@ -309,8 +309,7 @@ def test_mxm_mask_driven(gb, seed):
             D(D.S) << A.mxm(B, getattr(gb.semiring, sr))
             same_mat(D, exp2)
     finally:
-        _lib.lib.GrX_option_set(b"mxm_mask_mode", 1)
-        _lib.lib.GrX_option_set(b"mxm_masked_units_min_flops", 64 << 20)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -392,9 +391,7 @@ def test_hot_column_table(gb, seed):
         q(accum=getattr(gb.binary, accum) if accum else None) << B.mxv(q, getattr(gb.semiring, sr))
         same_vec(q, O.mxv(ob, oq, sr, w=oq, accum=accum))
     finally:
-        _lib.lib.GrX_option_set(b"hot_min_cols", 1 << 20)
-        _lib.lib.GrX_option_set(b"hot_k", 0)
-        _lib.lib.GrX_option_set(b"vec_pad_min_bytes", 1 << 20)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(16))
@@ -454,7 +451,7 @@ def test_push_direction(gb, seed):
         q(~vis.S, replace=True) << q.vxm(B, getattr(gb.semiring, sr))
         same_vec(q, O.vxm(oq, ob, sr, w=oq, mask=ovis, mask_comp=True, mask_struct=True, replace=True))
     finally:
-        _lib.lib.GrX_option_set(b"push_mode", 1)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(16))
@@ -541,16 +538,7 @@ def test_long_short_row_split(gb, seed):
         q(~mk.S, replace=True) << B.mxv(q, getattr(gb.semiring, sr))
         same_vec(q, O.mxv(ob, oq, sr, w=oq, mask=O.OVec(m, mi, mv, "BOOL"), mask_comp=True, mask_struct=True, replace=True))
     finally:
-        _lib.lib.GrX_option_set(b"split_min_nnz", 1 << 22)
-        _lib.lib.GrX_option_set(b"split_min_len", 0)
-        _lib.lib.GrX_option_set(b"push_mode", 1)
-        _lib.lib.GrX_option_set(b"short_kernel", DEFAULT_SHORT_KERNEL)
-        _lib.lib.GrX_option_set(b"hot_min_cols", 1 << 20)
-        _lib.lib.GrX_option_set(b"hot_k", 0)
-        _lib.lib.GrX_option_set(b"long_sub", 0)
-        _lib.lib.GrX_option_set(b"long_sub_min_len", 0)
-        _lib.lib.GrX_option_set(b"long_kernel", DEFAULT_LONG_KERNEL)
-        _lib.lib.GrX_option_set(b"long_classes", 16)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(21))
@@ -618,10 +606,7 @@ def test_hot_cold_strips(gb, seed):
                 same_vec(w2, O.mxv(oa, ouf, sr2, w=O.OVec(m, wi, wv, tname), mask=O.OVec(m, mi, mv, "BOOL"), mask_comp=comp, mask_struct=True,
                                    accum=accum, replace=repl))
     finally:
-        for name, val in ((b"split_min_nnz", 1 << 22), (b"split_min_len", 0), (b"push_mode", 1), (b"hot_min_cols", 1 << 20), (b"hot_k", 0),
-                          (b"long_kernel", DEFAULT_LONG_KERNEL), (b"long_classes", 16), (b"vec_pad_min_bytes", 1 << 20),
-                          (b"short_kernel", DEFAULT_SHORT_KERNEL)):
-            _lib.lib.GrX_option_set(name, val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -665,9 +650,7 @@ def test_cold_tiles_many_long_rows(gb, seed):
         same_vec(w, exp)
         same_vec(A.mxv(u, getattr(gb.semiring, sr)).new(), exp_plain)
     finally:
-        for name, val in ((b"split_min_nnz", 1 << 22), (b"split_min_len", 0), (b"push_mode", 1), (b"hot_min_cols", 1 << 20), (b"hot_k", 0),
-                          (b"long_kernel", DEFAULT_LONG_KERNEL), (b"long_sub", 0), (b"vec_pad_min_bytes", 1 << 20)):
-            _lib.lib.GrX_option_set(name, val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -726,9 +709,7 @@ def test_split_survives_mixed_calls_and_option_changes(gb, seed):
             red2 = A.reduce_rowwise(gb.monoid.plus).new()
             assert red2.isequal(red)
     finally:
-        for name, val in ((b"split_min_nnz", 1 << 22), (b"split_min_len", 0), (b"push_mode", 1), (b"hot_min_cols", 1 << 20), (b"hot_k", 0),
-                          (b"long_kernel", DEFAULT_LONG_KERNEL), (b"long_classes", 16), (b"vec_pad_min_bytes", 1 << 20)):
-            _lib.lib.GrX_option_set(name, val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -775,12 +756,7 @@ def test_long_rows_many_chunks(gb, seed, request):
         same_vec(w, exp)
         same_vec(A.mxv(u, getattr(gb.semiring, sr)).new(), exp_nomask)
     finally:
-        _lib.lib.GrX_option_set(b"split_min_nnz", 1 << 22)
-        _lib.lib.GrX_option_set(b"split_min_len", 0)
-        _lib.lib.GrX_option_set(b"push_mode", 1)
-        _lib.lib.GrX_option_set(b"long_kernel", DEFAULT_LONG_KERNEL)
-        _lib.lib.GrX_option_set(b"long_sub", 0)
-        _lib.lib.GrX_option_set(b"long_sub_min_len", 0)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(22))
@@ -953,7 +929,7 @@ def test_pair_over_full_operand(gb, seed):
                 w2(**kw) << u.vxm(A.T, getattr(gb.semiring, sr))
                 same_vec(w2, exp)
         finally:
-            _lib.lib.GrX_option_set(b"debug_flags", 0)
+            assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -995,12 +971,7 @@ def test_long_rows_terminal_monoids(gb, seed):
             w(~mk.S, replace=True) << A.mxv(u, getattr(gb.semiring, sr))
             same_vec(w, exp_m)
     finally:
-        _lib.lib.GrX_option_set(b"debug_flags", 0)
-        _lib.lib.GrX_option_set(b"split_min_nnz", 1 << 22)
-        _lib.lib.GrX_option_set(b"push_mode", 1)
-        _lib.lib.GrX_option_set(b"long_kernel", DEFAULT_LONG_KERNEL)
-        _lib.lib.GrX_option_set(b"hot_min_cols", 1 << 20)
-        _lib.lib.GrX_option_set(b"hot_k", 0)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(8))
@@ -1041,9 +1012,7 @@ def test_reductions_over_split_matrices(gb, seed):
                 w(mk.V) << A.mxv(u, getattr(gb.semiring, sr))
                 same_vec(w, O.mxv(oa, O.OVec(n, ui, uv, tname), sr, mask=O.OVec(m, mi, mv, "BOOL")))
     finally:
-        _lib.lib.GrX_option_set(b"debug_flags", 0)
-        _lib.lib.GrX_option_set(b"split_min_nnz", 1 << 22)
-        _lib.lib.GrX_option_set(b"split_min_len", 0)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -1086,7 +1055,7 @@ def test_mxm_streamed_row_batches(gb, seed, request):
                 assert nb.value >= 1 and (budget > 1 or nb.value > m // 4) and (budget < (1 << 30) or nb.value == 1)
         assert all(a == b for a, b in sums.values())
     finally:
-        _lib.lib.GrX_option_set(b"mxm_checksum_pass", 0)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("groups", [0, 4])
@@ -1126,8 +1095,7 @@ def test_mxm_streamed_checksum_through_the_unit_kernels(gb, groups, request):
             assert _lib.lib.GrX_mxm_streamed(sr._carg, A._carg, B._carg, budget, ctypes.byref(nv), ctypes.byref(cs), ctypes.byref(fl), ctypes.byref(nb)) == 0
             assert nv.value == ref.nnz and cs.value == int(ref.data.sum())
     finally:
-        for name, val in dict(mxm_unit_min_flops=1024, mxm_window_groups=0, mxm_unit_dense=4096).items():
-            _lib.lib.GrX_option_set(name.encode(), val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 def test_mxm_wide_heavy_rows(gb):
@@ -1194,7 +1162,7 @@ def test_mxm_unit_classes(gb, sr, tname, pool):
             _lib.lib.GrX_option_set(b"mxm_bitmap_pool_cap", pool)
         C = A.mxm(B, getattr(gb.semiring, sr)).new()
     finally:
-        _lib.lib.GrX_option_set(b"mxm_bitmap_pool_cap", (1 << 31) - 1)
+        assert _lib.lib.GrX_options_reset() == 0
     oc = O.mxm(O.OMat.from_coo(ar, ac, av, m, k, tname), O.OMat.from_coo(br, bc, bv, k, n, tname), sr)
     cp, cj, cx = C.to_csr()
     assert np.array_equal(cp.astype(np.int64), oc.indptr) and np.array_equal(cj.astype(np.int64), oc.indices)
@@ -1248,8 +1216,7 @@ def test_mxm_very_wide(gb):
         _lib.lib.GrX_option_set(b"mxm_masked_units_min_flops", 0)
         D = A.mxm(B, gb.semiring.plus_times).new(mask=M.S)
     finally:
-        _lib.lib.GrX_option_set(b"mxm_mask_mode", 1)
-        _lib.lib.GrX_option_set(b"mxm_masked_units_min_flops", 64 << 20)
+        assert _lib.lib.GrX_options_reset() == 0
     want = ref.multiply(sp.csr_matrix((np.ones(mr.size), (mr, mc)), shape=(m, n)).astype(bool)).tocsr()
     want.sort_indices()
     dp, dj, dx = D.to_csr()
@@ -1361,10 +1328,7 @@ def _mxm_units_case(gb, seed, on_gpu, nwin_hi=6, groups=0):
         else:
             same_mat(C, exp)
     finally:
-        for name, val in dict(mxm_unit_small=512, mxm_unit_mid=1024, mxm_unit_dense=4096, mxm_bitmap_pool_cap=(1 << 31) - 1,
-                              mxm_unit_min_flops=1024, mxm_masked_units_min_flops=64 << 20, mxm_mask_mode=1, mxm_sym_windows=8,
-                              mxm_window_groups=0).items():
-            _lib.lib.GrX_option_set(name.encode(), val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(28))
@@ -1456,9 +1420,7 @@ def test_mxm_complemented_mask_fused(gb, seed, request):
             else:
                 same_mat(C, exp)
     finally:
-        for name, val in dict(mxm_unit_small=512, mxm_unit_mid=1024, mxm_unit_dense=4096, mxm_bitmap_pool_cap=(1 << 31) - 1,
-                              mxm_unit_min_flops=1024, mxm_mask_mode=1, mxm_sym_windows=8).items():
-            _lib.lib.GrX_option_set(name.encode(), val)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(24))
@@ -1516,8 +1478,7 @@ def test_matrix_write_rule_wavefront_merge(gb, seed, request):
             C(**kw) << A.mxm(B, getattr(gb.semiring, sr))
             same_mat(C, exp)
     finally:
-        _lib.lib.GrX_option_set(b"mxm_mask_mode", 1)
-        _lib.lib.GrX_option_set(b"mat_write_kernel", 1)
+        assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("sr,tname", [("plus_times", "INT64"), ("min_plus", "FP64"), ("any_pair", "BOOL"), ("plus_pair", "UINT16")])
@@ -1562,7 +1523,7 @@ def test_mxm_masked_unit_classes(gb, sr, tname):
         _lib.lib.GrX_option_set(b"mxm_masked_units_min_flops", 0)  # (small products keep the row kernels by default)
         C(M.S) << A.mxm(B, getattr(gb.semiring, sr))
     finally:
-        _lib.lib.GrX_option_set(b"mxm_masked_units_min_flops", 64 << 20)
+        assert _lib.lib.GrX_options_reset() == 0
     om = O.OMat.from_coo(mr, mc, np.ones(mr.size, bool), m, n, "BOOL")
     oc = O.mxm(O.OMat.from_coo(ar, ac, av, m, k, tname), O.OMat.from_coo(br, bc, bv, k, n, tname), sr, mask=om, mask_struct=True)
     cp, cj, cx = C.to_csr()
@@ -1722,5 +1683,4 @@ def test_push_small_frontiers_in_one_workgroup(gb, seed):
             w7 << f.vxm(A, semi)  # (and the counters were left clean)
             same_vec(w7, O.vxm(of, oa, sr))
     finally:
-        _lib.lib.GrX_option_set(b"push_mode", 1)
-        _lib.lib.GrX_option_set(b"push_small", 1)
+        assert _lib.lib.GrX_options_reset() == 0

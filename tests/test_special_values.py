@@ -9,17 +9,12 @@ from oracle import grb_oracle as O
 from tests.backend import DEVICES, bind
 from tests.values import ALL_TYPES, FP_TYPES, plus_within_bound, rand_vals, same_fp, same_mat, same_vec, shape_rows
 
-DEFAULT_SHORT_KERNEL, DEFAULT_LONG_KERNEL = 6, 5
+DEFAULT_LONG_KERNEL = 5
 
 SPLIT = ((b"split_min_nnz", 1), (b"split_min_len", 8), (b"push_mode", 0))
 ORDER_OPTS = ((b"order_min_nnz", 1), (b"lean_min_nnz", 1), (b"split_min_nnz", 1), (b"split_min_len", 8), (b"push_mode", 0), (b"hot_min_cols", 8),
               (b"lazy_layout", 0), (b"vec_pad_min_bytes", 0), (b"rows_head_min_groups", 1), (b"order_mode", 1), (b"hot_k", 256),
               (b"hub_min_len", 200))
-RESTORE = ((b"order_min_nnz", 24 << 20), (b"lean_min_nnz", 48 << 20), (b"split_min_nnz", 1 << 22), (b"split_min_len", 0), (b"push_mode", 1),
-           (b"hot_min_cols", 1 << 20), (b"hot_k", 0), (b"lazy_layout", 1), (b"vec_pad_min_bytes", 1 << 20), (b"long_classes", 16),
-           (b"order_mode", 1), (b"hub_min_len", 1024), (b"rows_head_min_groups", 16384), (b"short_kernel", DEFAULT_SHORT_KERNEL),
-           (b"long_kernel", DEFAULT_LONG_KERNEL), (b"long_sub", 0), (b"long_sub_min_len", 0), (b"value_dict", 1), (b"fill_absent", 1),
-           (b"mxm_mask_mode", 1), (b"mxm_masked_units_min_flops", 64 << 20), (b"mxm_bitmap_pool_cap", (1 << 31) - 1))
 
 
 @pytest.fixture(params=DEVICES)
@@ -32,6 +27,12 @@ def set_opts(opts):
 
     for name, val in opts:
         assert _lib.lib.GrX_option_set(name, val) == 0, name
+
+
+def reset_opts():
+    from graphblas_amd import _lib
+
+    assert _lib.lib.GrX_options_reset() == 0
 
 
 def semirings_for(tname):
@@ -161,7 +162,7 @@ def test_mxv_paths(gb, path, tname):
             exp = O.mxv(oa, ou, sr, w=O.OVec(m, wi, wv, tname), mask=O.OVec(m, mi, mv, tname), mask_comp=comp, accum=accum)
             same_vec(w, exp, zero_sign_rule(monoid, accum), (path, tname, sr, "masked"))
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("tname", FP_TYPES)
@@ -184,7 +185,7 @@ def test_mxv_plus_over_reals_within_bound(gb, tname):
                 gi, gv = A.mxv(u, getattr(gb.semiring, f"plus_{mult}")).new().to_coo()
                 plus_within_bound(gi, gv, oa, ou, mult, (tname, mult, opts))
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 def test_value_dictionary_and_fill_with_negatives(gb):
@@ -223,7 +224,7 @@ def test_value_dictionary_and_fill_with_negatives(gb):
                         assert st["fill_absent"] == (1 if (vd and bad is None and uvals is uv) else 0), (where, st)
                         same_vec(got, O.mxv(oa, O.OVec(n, ui, uvals, "FP32"), sr), sr.split("_")[0], where)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("tname", ALL_TYPES)
@@ -263,7 +264,7 @@ def test_vxm_paths(gb, tname, push):
             exp = O.vxm(ou, oa, sr, w=O.OVec(n, wi, wv, tname), mask=O.OVec(n, mi, mv, "BOOL"), mask_comp=True, mask_struct=True, accum=accum)
             same_vec(w, exp, zero_sign_rule(monoid, accum), (push, tname, sr, "masked"))
     finally:
-        _lib.lib.GrX_option_set(b"push_mode", 1)
+        reset_opts()
 
 
 MXM_PATHS = ("rows", "mask_driven", "mask_units", "comp_mask", "units")
@@ -330,7 +331,7 @@ def test_mxm_paths(gb, tname, path):
                 got = A.mxm(B, S).new(mask=M.V)
                 same_mat(got, O.mxm(oa, ob, sr, mask=om), monoid, (path, tname, sr, "value mask"))
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("tname", [t for t in ALL_TYPES if t not in ("BOOL",) + FP_TYPES])
@@ -389,7 +390,7 @@ def test_value_dictionary_padding_under_plus_times(gb):
         at = np.searchsorted(gi, negzero)
         assert np.array_equal(gi[at], negzero) and np.all(gv[at] == 0) and np.all(np.signbit(gv[at])), gv[at]
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 def test_fill_limit(gb):
@@ -420,7 +421,7 @@ def test_fill_limit(gb):
                 assert st["ordered"] == 1 and st["fill_absent"] == want, (sr, near, st)
                 same_vec(got, O.mxv(oa, O.OVec(n, ui, uv, "FP32"), sr), sr.split("_")[0], (sr, near))
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("tname", ALL_TYPES)

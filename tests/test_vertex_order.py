@@ -18,9 +18,6 @@ from tests.test_random_parity import rand_vals, rand_vec, same_vec
 
 ORDER_OPTS = ((b"order_min_nnz", 1), (b"lean_min_nnz", 1), (b"split_min_nnz", 1), (b"split_min_len", 8), (b"push_mode", 0), (b"hot_min_cols", 8),
               (b"lazy_layout", 0), (b"vec_pad_min_bytes", 0), (b"rows_head_min_groups", 1))
-RESTORE = ((b"order_min_nnz", 24 << 20), (b"lean_min_nnz", 48 << 20), (b"split_min_nnz", 1 << 22), (b"split_min_len", 0), (b"push_mode", 1),
-           (b"hot_min_cols", 1 << 20), (b"hot_k", 0), (b"lazy_layout", 1), (b"vec_pad_min_bytes", 1 << 20), (b"long_classes", 16), (b"order_mode", 1), (b"hub_min_len", 1024), (b"rows_head_min_groups", 16384), (b"rows_head", 1),
-           (b"rows_tile", 1), (b"rtile_rows", 8192), (b"rtile_entries", 49152), (b"bool_probe", 8), (b"stream_nt_min_nnz", 48 << 20), (b"cold_in_rows", 0), (b"rtile_pack", 1), (b"strip_slot16", 1), (b"ctile_pack", 0), (b"lazy_tagged", 1))
 
 
 @pytest.fixture(params=DEVICES)
@@ -47,6 +44,12 @@ def set_opts(opts):
 
     for name, val in opts:
         assert _lib.lib.GrX_option_set(name, val) == 0, name
+
+
+def reset_opts():
+    from graphblas_amd import _lib
+
+    assert _lib.lib.GrX_options_reset() == 0
 
 
 @pytest.mark.parametrize("seed", range(21))
@@ -109,7 +112,7 @@ def test_ordered_product_matches_the_oracle(gb, seed):
         same_vec(u, ou)
         same_vec(mk, om)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -178,7 +181,7 @@ def test_ordered_vectors_through_every_exit(gb, seed):
         assert bits.tolist() == has.tolist()
         assert np.asarray(vals_t.cpu())[has].tolist() == dense[has].tolist()
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("tname", ["FP32", "FP64"])
@@ -205,7 +208,7 @@ def test_fp_plus_reduction_does_not_depend_on_the_stored_order(gb, tname):
             fresh = gb.Vector.from_coo(wi, wv, dtype=tname, size=n)
             assert got == fresh.reduce(mon).new().value
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 def _on_gpu():
@@ -294,7 +297,7 @@ def test_sssp_and_bfs_loops_stay_ordered(gb, seed):
         #  though q is its own output)
         assert any(m == 1 and fe in (2, 3) for m, _, fe in conv), conv  # (2: the LDS head of the row groups; 3: the sorted row tiles, round 5)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("case", ["256_values", "257_values", "with_inf", "dict_off"])
@@ -330,7 +333,7 @@ def test_value_dictionary_boundaries(gb, case):
                 assert gi.tolist() == exp.idx.tolist()
                 np.testing.assert_array_equal(gv, exp.vals)
     finally:
-        set_opts(RESTORE + ((b"value_dict", 1),))
+        reset_opts()
 
 
 def test_ordered_vectors_in_unusual_flows(gb):
@@ -416,7 +419,7 @@ def test_ordered_vectors_in_unusual_flows(gb):
         same_vec(r, e2)
         assert A2.mxv(u, gb.semiring.min_plus).new().isequal(r) and device.last_stats()["pinned_natural"] == 0
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("sr", ["min_plus", "max_plus"])
@@ -457,7 +460,7 @@ def test_sparse_operand_run_as_full_with_absorbing_fill(gb, sr):
                 w(accum=getattr(gb.binary, acc)) << A.mxv(u, getattr(gb.semiring, sr))
                 same_vec(w, O.mxv(oa, ou, sr, w=O.OVec(n, wi, wv, "FP32"), accum=acc))
     finally:
-        set_opts(RESTORE + ((b"fill_absent", 1),))
+        reset_opts()
 
 
 def test_view_held_across_an_ordered_product_stays_natural(gb):
@@ -500,7 +503,7 @@ def test_view_held_across_an_ordered_product_stays_natural(gb):
         A.mxv(u, gb.semiring.min_plus).new()
         assert device.last_stats()["ordered"] == 1
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(18))
@@ -578,7 +581,7 @@ def test_sorted_row_tiles_match_the_oracle(gb, seed):
         assert device.last_stats()["fused_epilogue"] == 1
         same_vec(w3, exp)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -624,7 +627,7 @@ def test_sorted_row_tiles_bool_step(gb, seed):
         assert device.last_stats()["fused_epilogue"] in (1, 2)
         same_vec(w3, exp)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -662,7 +665,7 @@ def test_bottom_up_probe_of_long_bool_rows(gb, seed):
             same_vec(w, exp)
             same_vec(A.mxv(u, getattr(gb.semiring, sr)).new(), exp_nomask)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(10))
@@ -727,7 +730,7 @@ def test_ranked_hint_orders_without_a_permutation(gb, seed):
         w2(~mk.S, accum=accum, replace=repl) << A.mxv(u, getattr(gb.semiring, sr))
         same_vec(w2, exp)
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 @pytest.mark.parametrize("seed", range(8))
@@ -796,7 +799,7 @@ def test_shard_setup_orders_a_row_block_by_global_column_counts(gb, seed):
         assert device.last_stats()["ordered"] == 0 and device.last_stats()["pinned_natural"] == 1
         same_vec(w, expected[0])
     finally:
-        set_opts(RESTORE)
+        reset_opts()
 
 
 def test_shard_setup_argument_errors(gb):
