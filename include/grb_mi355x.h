@@ -322,7 +322,9 @@ GrB_Info GrX_mxm_streamed(const GrB_Semiring semiring, const GrB_Matrix A, const
                           uint64_t *nvals, uint64_t *checksum, uint64_t *flops, uint64_t *batches);
 /* Same shape, same pattern and values equal (rel_tol = abs_tol = 0) or close (|a - b| <= max(rel_tol max(|a|, |b|), abs_tol), the
  * reference's _isclose, core/operator/binary.py:329), compared on the
- * device in a common type (reference Matrix.isequal / isclose, core/matrix.py:373-467, do it with eWiseMult + reduce). */
+ * device in a common type (reference Matrix.isequal / isclose, core/matrix.py:373-467, do it with eWiseMult + reduce).  The common type
+ * is the one the host's dtypes.unify gives the two types -- numpy's promote_types, the same table: INT8 / UINT8 -> INT16, INT8 / UINT16 ->
+ * INT32, INT64 / UINT64 -> FP64, FP32 / INT32 -> FP64 -- so no value changes on its way into it: INT8 -1 and UINT8 255 are unequal. */
 GrB_Info GrX_Matrix_isclose(bool *result, const GrB_Matrix A, const GrB_Matrix B, double rel_tol, double abs_tol);
 /* A copy with the values cast to `type`, made on the device (reference dup(dtype=...), core/matrix.py:469-497 and
  * core/vector.py:392-420: a new object of the target type, then `rv << self`). */

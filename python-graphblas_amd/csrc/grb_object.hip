@@ -1064,6 +1064,30 @@ static void matrix_export_typed(GB_Matrix_opaque *A, uint64_t *Ap, uint64_t *Ai,
     }
 }
 
+// The type in which two values of different types are compared: the table of the host's dtypes.unify (python-graphblas_amd/dtypes.py;
+// reference core/dtypes.py:552-568), which is numpy's promote_types over the 11 builtin types, written out.  Rows and columns in the
+// order of the type codes.
+static int unified_type(int a, int b)
+{
+    enum { B = TC_BOOL, I8 = TC_INT8, I16 = TC_INT16, I32 = TC_INT32, I64 = TC_INT64, U8 = TC_UINT8, U16 = TC_UINT16, U32 = TC_UINT32,
+           U64 = TC_UINT64, F32 = TC_FP32, F64 = TC_FP64 };
+    static const int8_t table[TC_COUNT][TC_COUNT] = {
+        /* BOOL   */ {  B,  I8, I16, I32, I64,  U8, U16, U32, U64, F32, F64},
+        /* INT8   */ { I8,  I8, I16, I32, I64, I16, I32, I64, F64, F32, F64},
+        /* INT16  */ {I16, I16, I16, I32, I64, I16, I32, I64, F64, F32, F64},
+        /* INT32  */ {I32, I32, I32, I32, I64, I32, I32, I64, F64, F64, F64},
+        /* INT64  */ {I64, I64, I64, I64, I64, I64, I64, I64, F64, F64, F64},
+        /* UINT8  */ { U8, I16, I16, I32, I64,  U8, U16, U32, U64, F32, F64},
+        /* UINT16 */ {U16, I32, I32, I32, I64, U16, U16, U32, U64, F32, F64},
+        /* UINT32 */ {U32, I64, I64, I64, I64, U32, U32, U32, U64, F64, F64},
+        /* UINT64 */ {U64, F64, F64, F64, F64, U64, U64, U64, U64, F64, F64},
+        /* FP32   */ {F32, F32, F32, F64, F64, F32, F32, F64, F64, F32, F64},
+        /* FP64   */ {F64, F64, F64, F64, F64, F64, F64, F64, F64, F64, F64},
+    };
+    if (a < 0 || a >= TC_COUNT || b < 0 || b >= TC_COUNT) fail(GrB_INVALID_OBJECT, "unknown type code");
+    return table[a][b];
+}
+
 }  // namespace grb
 
 using namespace grb;
@@ -1305,9 +1329,10 @@ extern "C" GrB_Info GrX_Matrix_isclose(bool *result, const GrB_Matrix A, const G
         *result = true;
         return GrB_SUCCESS;
     }
-    // values in a common type: the wider of the two (FP64 when they differ in kind)
-    int ct = A->type->code;
-    if (B->type->code != ct) ct = (A->type->code >= TC_FP32 || B->type->code >= TC_FP32) ? TC_FP64 : (A->type->size >= B->type->size ? A->type->code : B->type->code);
+    // values in the type the host's dtypes.unify gives the pair (numpy's promote_types, reference core/dtypes.py:552-568): a type that
+    // holds every value of both -- INT8 / UINT8 -> INT16, INT64 / UINT64 -> FP64, FP32 / INT32 -> FP64 -- never the wider of the two,
+    // in which a wrapping cast makes -1 equal to 2^k - 1
+    const int ct = unified_type(A->type->code, B->type->code);
     struct Owned {  // (typecast copies are released on every way out, also when a launch or the read-back throws)
         GB_Matrix_opaque *p = nullptr;
         ~Owned() { if (p) matrix_free(p); }

@@ -480,7 +480,9 @@ def test_power_masked_final_product(gb, A):
 
 def test_masked_transpose(gb, A):
     """``C(mask, accum, replace) << A.T`` -> GrB_transpose with the write rule (reference core/base.py:401-411): equal to the
-    product of the identity matrix with the transposed operand under the same mask / accumulator (mxm's own write rule)."""
+    product of the identity matrix with the transposed operand under the same mask / accumulator (mxm's own write rule).  Both sides of
+    that comparison share the library's write rule; the comparison with the oracle is one assertion at the end here and, across masks,
+    accumulators, replace, types and aliasing, tests/test_object_layer.py::test_masked_transpose_against_the_oracle."""
     eye = gb.Matrix.from_coo(range(7), range(7), [1] * 7, dtype=A.dtype)
     M = gb.Matrix.from_coo([0, 1, 3, 3, 6, 6, 5], [1, 4, 0, 2, 2, 3, 2], [True, False, True, True, True, False, True], nrows=7, ncols=7)
     # (the plain transpose's literal, graphblas/tests/test_matrix.py:1700-1707: reference_literals.json transpose)
@@ -496,6 +498,20 @@ def test_masked_transpose(gb, A):
     D = A.dup()
     D(A.S) << eye.mxm(A.T, gb.semiring.plus_times)
     assert heq(C, D)
+    # ... and against the oracle: its own transpose under its own write rule
+    from oracle import grb_oracle as O
+
+    ar, ac, av = [3, 0, 3, 5, 6, 0, 6, 1, 6, 2, 4, 1], [0, 1, 2, 2, 2, 3, 3, 4, 4, 5, 5, 6], [3, 2, 3, 1, 5, 3, 7, 8, 3, 1, 7, 4]  # (fixture A)
+    oa = O.OMat.from_coo(ar, ac, np.asarray(av, np.int64), 7, 7, "INT64")
+    om = O.OMat.from_coo([0, 1, 3, 3, 6, 6, 5], [1, 4, 0, 2, 2, 3, 2], np.array([True, False, True, True, True, False, True]), 7, 7, "BOOL")
+    oeye = O.OMat.from_coo(np.arange(7), np.arange(7), np.ones(7, np.int64), 7, 7, "INT64")
+    assert A.dtype.name == "INT64"
+    C = A.dup()
+    C(~M.V, gb.binary.plus, replace=True) << A.T
+    exp = O.mxm(oeye, oa.transpose(), "any_second", C=oa, mask=om, mask_comp=True, accum="plus", replace=True)
+    Cp, Cj, Cx = C.to_csr()
+    assert Cp.astype(np.int64).tolist() == exp.indptr.tolist() and Cj.astype(np.int64).tolist() == exp.indices.tolist()
+    assert Cx.tolist() == exp.values.tolist()
 
 
 def test_index_max(gb):
