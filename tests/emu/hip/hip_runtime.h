@@ -208,9 +208,11 @@ inline long long atomicMin(long long *p, long long v) { auto o = *p; if (v < o) 
 inline long long atomicMax(long long *p, long long v) { auto o = *p; if (v > o) *p = v; return o; }
 inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) { auto o = *p; if (v < o) *p = v; return o; }
 inline unsigned long long atomicMax(unsigned long long *p, unsigned long long v) { auto o = *p; if (v > o) *p = v; return o; }
-inline float atomicMin(float *p, float v) { auto o = *p; if (v < o || o != o) *p = v; return o; }
-inline float atomicMax(float *p, float v) { auto o = *p; if (v > o || o != o) *p = v; return o; }
-inline double atomicMin(double *p, double v) { auto o = *p; if (v < o || o != o) *p = v; return o; }
-inline double atomicMax(double *p, double v) { auto o = *p; if (v > o || o != o) *p = v; return o; }
+// (floating point: HIP's compare-and-swap form stores only while slot > v / slot < v, so a NaN slot is KEPT; the hardware instruction
+//  replaces it.  The emulator takes the form that keeps it: a kernel that seeds a slot with NaN has to finish that slot itself)
+inline float atomicMin(float *p, float v) { auto o = *p; if (v < o) *p = v; return o; }
+inline float atomicMax(float *p, float v) { auto o = *p; if (v > o) *p = v; return o; }
+inline double atomicMin(double *p, double v) { auto o = *p; if (v < o) *p = v; return o; }
+inline double atomicMax(double *p, double v) { auto o = *p; if (v > o) *p = v; return o; }
 inline unsigned int atomicXor(unsigned int *p, unsigned int v) { auto o = *p; *p = o ^ v; return o; }
 inline unsigned long long atomicXor(unsigned long long *p, unsigned long long v) { auto o = *p; *p = o ^ v; return o; }

@@ -812,7 +812,8 @@ def test_vector_assign_reduce_random(gb, seed):
 @pytest.mark.parametrize("seed", range(22))
 def test_vector_ewise_random(gb, seed):
     """eWiseAdd / eWiseMult against a numpy restatement (union / intersection, then the oracle's write rule): every type,
-    masks, accumulators, replace, output aliased with an input, mixed input types."""
+    masks, accumulators, replace, output aliased with an input.  u, v and w share one type here; operands and an output of three
+    different types are tests/test_vector_kernels.py::test_ewise_mixed_types."""
     rng = np.random.default_rng(1900 + seed)
     tname = ["BOOL", "INT8", "INT16", "INT32", "INT64", "UINT8", "UINT16", "UINT32", "UINT64", "FP32", "FP64"][seed % 11]
     n = int(rng.integers(1, 500)) if seed % 5 else [1, 64, 65, 128][seed % 4]
