@@ -1753,6 +1753,7 @@ __global__ void k_mat_write(int64_t m, const int64_t *Cp, const int32_t *Cj, con
 }
 
 #include "grb_mxm_write.inc"
+#include "grb_mxm_ewise.inc"
 
 // ---------------------------------------------------------------------------------------------------
 // host side
@@ -2522,6 +2523,80 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
     if (ctx().blocking) sync_stream();
 }
 
+// C<Mask, replace> = accum(C, A (op) B), element-wise over the union (is_add) or the intersection of the patterns (reference
+// core/matrix.py ewise_add / ewise_mult -> GrB_Matrix_eWiseAdd_* / eWiseMult_*); the semantics of ewise_core (grb_vecops.hip), the
+// merge of grb_mxm_ewise.inc.  `op_in` / `ot`: the operator's code and type
+static void matrix_ewise_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, int op_in, int ot,
+                              GB_Matrix_opaque *A, GB_Matrix_opaque *B, MDesc f, bool is_add)
+{
+    const uint64_t a_rows = f.t0 ? A->ncols : A->nrows, a_cols = f.t0 ? A->nrows : A->ncols;
+    const uint64_t b_rows = f.t1 ? B->ncols : B->nrows, b_cols = f.t1 ? B->nrows : B->ncols;
+    if (a_rows != b_rows || a_cols != b_cols)
+        fail(GrB_DIMENSION_MISMATCH, "eWise: inputs are " + std::to_string(a_rows) + " x " + std::to_string(a_cols) + " and " + std::to_string(b_rows) +
+                                         " x " + std::to_string(b_cols));
+    if (C->nrows != a_rows || C->ncols != a_cols)
+        fail(GrB_DIMENSION_MISMATCH, "eWise: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the inputs " +
+                                         std::to_string(a_rows) + " x " + std::to_string(a_cols));
+    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "eWise: mask shape does not match the output");
+    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "eWise: accum operator type must equal the output type");
+    const bool cmp = op_is_comparison(op_in);
+    const int op = cmp ? op_in : canonical_op(ot, op_in);
+    const int tt = cmp ? (int)TC_BOOL : ot;  // type of the element-wise result
+    ctx().stats = GrX_Stats{};
+    if (!Mask && f.comp) {  // complement of "no mask": nothing may be written
+        if (f.replace) matrix_release_storage(C);
+        return;
+    }
+    if (C->nrows == 0 || C->ncols == 0) return;
+    GB_Matrix_opaque *Ae = f.t0 ? matrix_transpose_cached(A) : A;
+    GB_Matrix_opaque *Be = f.t1 ? matrix_transpose_cached(B) : B;
+    const int ctype = C->type->code;
+    GB_Matrix_opaque *Tm = nullptr;
+    if (Ae->nvals == 0 || Be->nvals == 0) {
+        // exact short cuts: the intersection with nothing is empty, the union with nothing a cast copy of the other operand
+        ctx().stats.method = 6;
+        if (!is_add || (Ae->nvals == 0 && Be->nvals == 0)) Tm = matrix_new(C->type, C->nrows, C->ncols);
+        else Tm = ewise_pass_through(Ae->nvals ? Ae : Be, ot, tt, ctype, Mask || accum);
+    } else {
+        ctx().stats.method = 8;
+        // operands in the operator's type (an iso operand: its one value)
+        DevPtr<char> a_cast, b_cast;
+        const void *Ax = Ae->d_val, *Bx = Be->d_val;
+        if (Ae->type->code != ot) {
+            const int64_t nv = Ae->iso ? 1 : Ae->nvals;
+            a_cast.p = (char *)dev_alloc(type_size(ot) * (size_t)nv);
+            cast_array(ot, a_cast.p, Ae->type->code, Ae->d_val, nv);
+            Ax = a_cast.p;
+        }
+        if (Be->type->code != ot) {
+            const int64_t nv = Be->iso ? 1 : Be->nvals;
+            b_cast.p = (char *)dev_alloc(type_size(ot) * (size_t)nv);
+            cast_array(ot, b_cast.p, Be->type->code, Be->d_val, nv);
+            Bx = b_cast.p;
+        }
+        Tm = ewise_merge(Ae, Ax, Be, Bx, ot, tt, op, is_add, cmp);
+    }
+    try {
+        // T in the output type
+        if (Tm->nvals && Tm->type->code != ctype) {
+            void *cv = dev_alloc(C->type->size * (size_t)Tm->nvals);
+            cast_array(ctype, cv, tt, Tm->d_val, Tm->nvals);
+            dev_free(Tm->d_val);
+            Tm->d_val = cv;
+        }
+        Tm->type = C->type;
+        // T is a fresh object, so C may alias A, B or the mask
+        if (C == A || C == B) matrix_invalidate_caches(C);
+        matrix_apply_write_rule(C, Mask, accum, Tm, f.replace, f.comp, f.structure);
+    } catch (...) {
+        matrix_free(Tm);
+        throw;
+    }
+    matrix_free(Tm);
+    ctx().stats.out_nvals = C->nvals;
+    if (ctx().blocking) sync_stream();
+}
+
 // ---- row-batched product with the output streamed through a bounded buffer ---------------------------------------------------
 // C = A (+.x) B of a power-law graph can outgrow any one GPU (R-MAT scale 22: 7.5e10 entries, 900 GB): the product is then run
 // over row batches of A whose products fit `budget_bytes`, each batch through the full two-pass pipeline (symbolic + numeric,
@@ -2693,6 +2768,31 @@ extern "C" GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
     mxm_core(C, Mask, accum, semiring, A, B, f);
     GRB_CATCH(errp(C))
 }
+
+// the _Semiring forms take the additive monoid (eWiseAdd) / the multiply operator (eWiseMult): C API 2.0 sections 4.3.4 / 4.3.5
+#define GRB_MATRIX_EWISE(FUNC, HANDLE, CODE, IS_ADD)                                                                              \
+    extern "C" GrB_Info FUNC(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const HANDLE op, const GrB_Matrix A, \
+                             const GrB_Matrix B, const GrB_Descriptor desc)                                                      \
+    {                                                                                                                             \
+        GRB_TRY                                                                                                                   \
+        require_init();                                                                                                           \
+        check_matrix(C, "C");                                                                                                     \
+        if (Mask) check_matrix(Mask, "Mask");                                                                                     \
+        check_matrix(A, "A");                                                                                                     \
+        check_matrix(B, "B");                                                                                                     \
+        if (!op) fail(GrB_NULL_POINTER, "eWise: operator is NULL");                                                               \
+        MDesc f;                                                                                                                  \
+        if (desc) { f.replace = desc->replace; f.comp = desc->comp; f.structure = desc->structure; f.t0 = desc->t0; f.t1 = desc->t1; } \
+        matrix_ewise_core(C, Mask, accum, op->CODE, op->type, A, B, f, IS_ADD);                                                  \
+        GRB_CATCH(errp(C))                                                                                                        \
+    }
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseAdd_BinaryOp, GrB_BinaryOp, op, true)
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseAdd_Monoid, GrB_Monoid, op, true)
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseAdd_Semiring, GrB_Semiring, monoid, true)
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_BinaryOp, GrB_BinaryOp, op, false)
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_Monoid, GrB_Monoid, op, false)
+GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_Semiring, GrB_Semiring, mult, false)
+#undef GRB_MATRIX_EWISE
 
 namespace grb {
 void preload_mxm() { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_window_offsets_wave)); (void)hipGetLastError(); }

@@ -1,0 +1,262 @@
+// grb_mxm_ewise.inc -- T = A (op) B element-wise on two matrices with sorted CSR rows: over the UNION of the patterns (eWiseAdd: an
+// entry one side alone holds passes through) or their INTERSECTION (eWiseMult), a WAVEFRONT per unit (part of grb_mxm.hip; DESIGN.md
+// section 4.6).
+//
+// Reference: graphblas/core/matrix.py ewise_add / ewise_mult -> GrB_Matrix_eWiseAdd_* / GrB_Matrix_eWiseMult_* (C API 2.0 sections
+// 4.3.4 / 4.3.5); the vector form is ewise_core of grb_vecops.hip, whose semantics these follow.
+//
+// The two-list case of the merge of grb_mxm_write.inc, with its helpers and its unit tables as they are:
+//   * a unit is a row, or -- for rows with more than WR_LONG entries in A and B together -- a (row, column piece) pair;
+//   * per step lane l loads entry l of the next chunk of A(i,:) and of B(i,:); the step's BOUND is the smaller last-loaded column
+//     over the lists that still have unloaded entries; every A entry up to the bound finds its partner in the B chunk by a 6-step
+//     search in LDS (and reads the partner's value there), every B entry up to the bound learns the same way whether A holds it;
+//   * an emitted entry's position = emitted entries of its own list before it + emitted entries of the other list below its column
+//     -- two popcounts of ballots; no atomics;
+//   * counts per unit -> one scan -> the same walk fills.
+// An iso operand is read as its single value.  Comparison operators write BOOL (k_ewise_cmp of grb_vecops.hip is the vector precedent).
+// LDS: 2 column chunks + 1 value chunk per wavefront = 2 KiB + 256 sizeof(T) per workgroup (k_mat_write_wave: 3 KiB + 256 sizeof(T)).
+#pragma once
+
+struct EwiseArgs {
+    const int64_t *Ap;
+    const int32_t *Aj;
+    const void *Ax;
+    int a_iso;
+    const int64_t *Bp;
+    const int32_t *Bj;
+    const void *Bx;
+    int b_iso;
+    int op;                // canonical binary operator, or a comparison code (CMP kernels)
+    // units (k_write_units_per_row / k_write_unit_rows of the write rule)
+    const int64_t *ubase;  // first unit of every row (m + 1)
+    const int32_t *urow;   // the row of every unit
+    int64_t n_units;
+    int piece_cols;        // columns per piece of a cut row
+    int64_t *ucount;       // count pass: entries the unit emits
+    const int64_t *uoff;   // fill pass: where the unit writes
+    int32_t *Tj;
+    void *Tx;
+};
+
+template <typename T>
+__device__ __forceinline__ bool ewise_compare(int op, T a, T b)
+{
+    switch (op) {
+    case OP_EQ: return a == b;
+    case OP_NE: return a != b;
+    case OP_GT: return a > b;
+    case OP_LT: return a < b;
+    case OP_GE: return a >= b;
+    default: return a <= b;
+    }
+}
+
+// T: the operator's type (both operands are in it); CMP: `op` is a comparison and the result BOOL
+template <typename T, bool UNION, bool FILL, bool CMP>
+__global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
+{
+    using TO = typename std::conditional<CMP, bool, T>::type;
+    constexpr int COL_END = 0x7fffffff;
+    __shared__ int s_a[4][64], s_b[4][64];
+    __shared__ T s_bv[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t unit = (int64_t)blockIdx.x * 4 + wv;
+    if (unit >= a.n_units) return;  // (uniform over the wavefront)
+    const int64_t row = a.urow[unit];
+    const int64_t u0 = a.ubase[row], pieces = a.ubase[row + 1] - u0;
+    int64_t pa = a.Ap[row], ea = a.Ap[row + 1], pb = a.Bp[row], eb = a.Bp[row + 1];
+    if (pieces > 1) {  // this wavefront's column piece of a long row
+        const int64_t piece = unit - u0;
+        const int64_t c_lo = piece * a.piece_cols, c_hi = c_lo + a.piece_cols;
+        const int k_lo = (int)c_lo, k_hi = (piece == pieces - 1 || c_hi >= COL_END) ? COL_END : (int)c_hi;
+        pa = wave_lower_bound(a.Aj, pa, ea, k_lo, lane);
+        ea = wave_lower_bound(a.Aj, pa, ea, k_hi, lane);
+        pb = wave_lower_bound(a.Bj, pb, eb, k_lo, lane);
+        eb = wave_lower_bound(a.Bj, pb, eb, k_hi, lane);
+    }
+    const T *Ax = (const T *)a.Ax, *Bx = (const T *)a.Bx;
+    TO *Tx = (TO *)a.Tx;
+    int *sa = s_a[wv], *sb = s_b[wv];
+    T *sbv = s_bv[wv];
+    const int op = a.op;
+    int64_t out = FILL ? a.uoff[unit] : 0, cnt = 0;
+    // (the intersection is complete as soon as one list is: what the other still holds has no partner)
+    while (UNION ? (pa < ea || pb < eb) : (pa < ea && pb < eb)) {
+        // ---- the next chunk of both lists
+        const bool a_in = pa + lane < ea, b_in = pb + lane < eb;
+        const int aj = a_in ? a.Aj[pa + lane] : COL_END, bj = b_in ? a.Bj[pb + lane] : COL_END;
+        T av = (T)0, bv = (T)0;
+        if (FILL && a_in) av = Ax[a.a_iso ? 0 : pa + lane];
+        if (FILL && b_in) bv = Bx[a.b_iso ? 0 : pb + lane];
+        sa[lane] = aj;
+        sb[lane] = bj;
+        sbv[lane] = bv;
+        // the step's bound: the smaller last-loaded column over the lists with entries still unloaded (v_readlane, as in k_mat_write_wave)
+        const int last_a = ea - pa > 64 ? __builtin_amdgcn_readlane(aj, 63) : COL_END, last_b = eb - pb > 64 ? __builtin_amdgcn_readlane(bj, 63) : COL_END;
+        const int bound = last_a < last_b ? last_a : last_b;
+        mw_sync();
+        const bool use_a = a_in && aj <= bound, use_b = b_in && bj <= bound;
+        bool emit_a = false, emit_b = false;
+        TO za = (TO)0, zb = (TO)0;
+        int lb_b = 0, lb_a = 0;
+        // ---- A entries: partner in the B chunk
+        if (use_a) {
+            lb_b = chunk_lower_bound(sb, aj);
+            const bool hb = lb_b < 64 && sb[lb_b] == aj;
+            emit_a = UNION || hb;
+            if (FILL) {
+                if (hb) {
+                    if constexpr (CMP) za = ewise_compare<T>(op, av, sbv[lb_b]);
+                    else za = apply_binop<T>(op, av, sbv[lb_b]);
+                } else {
+                    za = cast_value<TO, T>(av);
+                }
+            }
+        }
+        // ---- B entries without a partner in A
+        if (UNION && use_b) {
+            lb_a = chunk_lower_bound(sa, bj);
+            emit_b = !(lb_a < 64 && sa[lb_a] == bj);
+            zb = cast_value<TO, T>(bv);
+        }
+        const unsigned long long e_a = __ballot(emit_a), e_b = __ballot(emit_b);
+        if (FILL) {
+            const unsigned long long mine = bits_below(lane);
+            if (emit_a) {
+                const int64_t o = out + cnt + __popcll(e_a & mine) + __popcll(e_b & bits_below(lb_b));
+                a.Tj[o] = aj;
+                Tx[o] = za;
+            }
+            if (emit_b) {
+                const int64_t o = out + cnt + __popcll(e_b & mine) + __popcll(e_a & bits_below(lb_a));
+                a.Tj[o] = bj;
+                Tx[o] = zb;
+            }
+        }
+        cnt += __popcll(e_a) + __popcll(e_b);
+        pa += __popcll(__ballot(use_a));
+        pb += __popcll(__ballot(use_b));
+        mw_sync();
+    }
+    if (!FILL && lane == 0) a.ucount[unit] = cnt;
+}
+
+template <typename U>
+__global__ void k_ewise_bcast(U *out, int64_t n, const U *src)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = src[0];
+}
+
+template <typename T>
+static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea)
+{
+    const dim3 block(256);
+    if (is_add) {
+        if (cmp) hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, true>), grid, block, 0, ctx().stream, ea);
+        else hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, false>), grid, block, 0, ctx().stream, ea);
+    } else {
+        if (cmp) hipLaunchKernelGGL((k_mat_ewise_wave<T, false, true, true>), grid, block, 0, ctx().stream, ea);
+        else hipLaunchKernelGGL((k_mat_ewise_wave<T, false, true, false>), grid, block, 0, ctx().stream, ea);
+    }
+}
+
+// T (fresh storage, type `tt`) = A (op) B; Ax / Bx: the operands' values in the operator's type `ot` (one value when iso); both
+// operands hold entries
+static GB_Matrix_opaque *ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op,
+                                     bool is_add, bool cmp)
+{
+    GB_Matrix_opaque *Tm = matrix_new(type_of_code(tt), A->nrows, A->ncols);
+    try {
+        const int64_t m = (int64_t)A->nrows, ncols = (int64_t)A->ncols;
+        EwiseArgs ea{};
+        ea.Ap = A->d_ptr; ea.Aj = A->d_col; ea.Ax = Ax; ea.a_iso = A->iso ? 1 : 0;
+        ea.Bp = B->d_ptr; ea.Bj = B->d_col; ea.Bx = Bx; ea.b_iso = B->iso ? 1 : 0;
+        ea.op = op;
+        const int pieces = (int)std::min<int64_t>(WR_MAX_PIECES, std::max<int64_t>(1, ceil_div(ncols, (int64_t)16384)));
+        ea.piece_cols = (int)std::min<int64_t>(0x7fffffff, ceil_div(ncols, (int64_t)pieces));
+        DevBuf<int64_t> ubase(m + 1);
+        hipLaunchKernelGGL(k_write_units_per_row, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, ea.Ap, ea.Bp, m, pieces, ubase.p);
+        prim_exclusive_sum_i64(ubase.p, ubase.p, m + 1);
+        int64_t n_units = 0, nnzT = 0;
+        d2h(&n_units, ubase.p + m, sizeof(int64_t));
+        if (n_units == 0) {
+            ctx().stats.kernel_launches += 2;
+            return Tm;
+        }
+        DevBuf<int32_t> urow(n_units);
+        hipLaunchKernelGGL(k_write_unit_rows, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, m, urow.p);
+        DevBuf<int64_t> uoff(n_units + 1, true);
+        ea.ubase = ubase.p; ea.urow = urow.p; ea.n_units = n_units; ea.ucount = uoff.p;
+        const dim3 grid((unsigned)ceil_div(n_units, 4)), block(256);
+        // (the count pass reads no value: one instantiation per pattern rule)
+        if (is_add) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false>), grid, block, 0, ctx().stream, ea);
+        else hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, false, false, false>), grid, block, 0, ctx().stream, ea);
+        prim_exclusive_sum_i64(uoff.p, uoff.p, n_units + 1);
+        d2h(&nnzT, uoff.p + n_units, sizeof(int64_t));
+        ctx().stats.kernel_launches += 5;
+        if (nnzT) {
+            Tm->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
+            hipLaunchKernelGGL(k_write_rowptr, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p,
+                               (const int64_t *)uoff.p, m, Tm->d_ptr);
+            Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzT);
+            Tm->d_val = dev_alloc(type_size(tt) * (size_t)nnzT);
+            ea.uoff = uoff.p; ea.Tj = Tm->d_col; ea.Tx = Tm->d_val;
+            GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea); })
+            ctx().stats.kernel_launches += 2;
+        }
+        Tm->nvals = nnzT;
+        GRB_HIP(hipGetLastError());
+        sync_stream();  // (the unit tables are released at the end of this scope)
+        return Tm;
+    } catch (...) {
+        matrix_free(Tm);
+        throw;
+    }
+}
+
+// T = the entries of S as eWiseAdd passes them through when the other operand is empty: cast to the operator's type `ot`, to the
+// element-wise result type `tt`, then to `ctype`.  full_values: one value per entry even when S is iso (the write rule reads one value
+// per entry of T when it masks or accumulates)
+static GB_Matrix_opaque *ewise_pass_through(GB_Matrix_opaque *S, int ot, int tt, int ctype, bool full_values)
+{
+    GB_Matrix_opaque *Tm = matrix_cast_copy(S, ot);
+    if (Tm->nvals == 0) {
+        Tm->type = type_of_code(ctype);
+        return Tm;
+    }
+    try {
+        const int64_t nv = Tm->iso ? 1 : Tm->nvals;
+        int cur = ot;
+        for (const int next : {tt, ctype}) {
+            if (next == cur) continue;
+            void *nvp = dev_alloc(type_size(next) * (size_t)nv);
+            cast_array(next, nvp, cur, Tm->d_val, nv);
+            dev_free(Tm->d_val);
+            Tm->d_val = nvp;
+            cur = next;
+        }
+        Tm->type = type_of_code(ctype);
+        if (Tm->iso && full_values) {
+            const size_t size = type_size(ctype);
+            const int64_t n = Tm->nvals;
+            void *full = dev_alloc(size * (size_t)n);
+            const dim3 grid((unsigned)ceil_div(n, 256)), block(256);
+            switch (size) {
+            case 1: hipLaunchKernelGGL((k_ewise_bcast<uint8_t>), grid, block, 0, ctx().stream, (uint8_t *)full, n, (const uint8_t *)Tm->d_val); break;
+            case 2: hipLaunchKernelGGL((k_ewise_bcast<uint16_t>), grid, block, 0, ctx().stream, (uint16_t *)full, n, (const uint16_t *)Tm->d_val); break;
+            case 4: hipLaunchKernelGGL((k_ewise_bcast<uint32_t>), grid, block, 0, ctx().stream, (uint32_t *)full, n, (const uint32_t *)Tm->d_val); break;
+            default: hipLaunchKernelGGL((k_ewise_bcast<uint64_t>), grid, block, 0, ctx().stream, (uint64_t *)full, n, (const uint64_t *)Tm->d_val); break;
+            }
+            ctx().stats.kernel_launches += 1;
+            dev_free(Tm->d_val);
+            Tm->d_val = full;
+            Tm->iso = false;
+        }
+        GRB_HIP(hipGetLastError());
+        return Tm;
+    } catch (...) {
+        matrix_free(Tm);
+        throw;
+    }
+}

@@ -9,7 +9,8 @@
 //     codes GrB_select runs on (grb_select.hip); GrB_ROWINDEX / COLINDEX / DIAGINDEX_* are apply operators and stay handle-only;
 //   * GrB_Scalar for real (a host-side value + presence: the reference passes scalars by GrB_Scalar handle in C API 2.0 calls);
 //   * the entry points of the operations this library does not accelerate, with their C API 2.0 signatures, returning
-//     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip.)
+//     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip;
+//     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -256,15 +257,7 @@ static GrB_Info not_impl(GB_Vector_opaque *w, const char *fn)
 
 NI_V(GrB_Vector_apply, const GrB_Vector, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Vector, const GrB_Descriptor)
 NI_M(GrB_Matrix_apply, const GrB_Matrix, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Matrix, const GrB_Descriptor)
-NI_V(GrB_Vector_eWiseAdd_Semiring, const GrB_Vector, const GrB_BinaryOp, const GrB_Semiring, const GrB_Vector, const GrB_Vector, const GrB_Descriptor)
-NI_V(GrB_Vector_eWiseMult_Semiring, const GrB_Vector, const GrB_BinaryOp, const GrB_Semiring, const GrB_Vector, const GrB_Vector, const GrB_Descriptor)
 #define NI_MAT_BINARY(FN, HANDLE) NI_M(FN, const GrB_Matrix, const GrB_BinaryOp, const HANDLE, const GrB_Matrix, const GrB_Matrix, const GrB_Descriptor)
-NI_MAT_BINARY(GrB_Matrix_eWiseAdd_BinaryOp, GrB_BinaryOp)
-NI_MAT_BINARY(GrB_Matrix_eWiseAdd_Monoid, GrB_Monoid)
-NI_MAT_BINARY(GrB_Matrix_eWiseAdd_Semiring, GrB_Semiring)
-NI_MAT_BINARY(GrB_Matrix_eWiseMult_BinaryOp, GrB_BinaryOp)
-NI_MAT_BINARY(GrB_Matrix_eWiseMult_Monoid, GrB_Monoid)
-NI_MAT_BINARY(GrB_Matrix_eWiseMult_Semiring, GrB_Semiring)
 NI_MAT_BINARY(GrB_Matrix_kronecker_BinaryOp, GrB_BinaryOp)
 NI_MAT_BINARY(GrB_Matrix_kronecker_Monoid, GrB_Monoid)
 NI_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)

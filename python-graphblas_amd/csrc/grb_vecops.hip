@@ -681,7 +681,8 @@ extern "C" GrB_Info GrB_Vector_removeElement(GrB_Vector w, GrB_Index i)
 GRB_FOR_EACH_TYPE(GRB_VECOPS_TYPED)
 #undef GRB_VECOPS_TYPED
 
-#define GRB_EWISE(FUNC, HANDLE, IS_ADD)                                                                                        \
+// (the _Semiring forms take the additive monoid for eWiseAdd, the multiply operator for eWiseMult: C API 2.0 sections 4.3.4 / 4.3.5)
+#define GRB_EWISE(FUNC, HANDLE, CODE, IS_ADD)                                                                                      \
     extern "C" GrB_Info FUNC(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const HANDLE op, const GrB_Vector u,   \
                              const GrB_Vector v, const GrB_Descriptor desc)                                                      \
     {                                                                                                                          \
@@ -692,13 +693,15 @@ GRB_FOR_EACH_TYPE(GRB_VECOPS_TYPED)
         check_vector_any(u, "u");                                                                                              \
         check_vector_any(v, "v");                                                                                              \
         if (!op) fail(GrB_NULL_POINTER, "eWise: operator is NULL");                                                            \
-        ewise_core(w, mask, accum, op->op, op->type, u, v, desc, IS_ADD);                                                      \
+        ewise_core(w, mask, accum, op->CODE, op->type, u, v, desc, IS_ADD);                                                    \
         GRB_CATCH(errp(w))                                                                                                     \
     }
-GRB_EWISE(GrB_Vector_eWiseAdd_BinaryOp, GrB_BinaryOp, true)
-GRB_EWISE(GrB_Vector_eWiseAdd_Monoid, GrB_Monoid, true)
-GRB_EWISE(GrB_Vector_eWiseMult_BinaryOp, GrB_BinaryOp, false)
-GRB_EWISE(GrB_Vector_eWiseMult_Monoid, GrB_Monoid, false)
+GRB_EWISE(GrB_Vector_eWiseAdd_BinaryOp, GrB_BinaryOp, op, true)
+GRB_EWISE(GrB_Vector_eWiseAdd_Monoid, GrB_Monoid, op, true)
+GRB_EWISE(GrB_Vector_eWiseAdd_Semiring, GrB_Semiring, monoid, true)
+GRB_EWISE(GrB_Vector_eWiseMult_BinaryOp, GrB_BinaryOp, op, false)
+GRB_EWISE(GrB_Vector_eWiseMult_Monoid, GrB_Monoid, op, false)
+GRB_EWISE(GrB_Vector_eWiseMult_Semiring, GrB_Semiring, mult, false)
 #undef GRB_EWISE
 
 namespace grb {

@@ -1,7 +1,7 @@
 """Matrix / TransposedMatrix: the host-side mirror of graphblas/core/matrix.py for the path --
 constructor :190-203, ``__del__`` :218-225, ``build`` :627-681, ``from_coo`` :818-894, ``_from_csx``
-:992-1068, ``to_coo`` :525-594, ``_to_csx`` :1601-1645, ``isequal`` :373-415, ``mxv`` :2203-2262,
-``mxm`` :2264-2331, ``TransposedMatrix`` :3900-3960."""
+:992-1068, ``to_coo`` :525-594, ``_to_csx`` :1601-1645, ``isequal`` :373-415, ``ewise_add`` :1861-1950,
+``ewise_mult`` :1952-2041, ``mxv`` :2203-2262, ``mxm`` :2264-2331, ``TransposedMatrix`` :3900-3960."""
 from __future__ import annotations
 
 import ctypes
@@ -12,7 +12,7 @@ from . import _lib
 from .base import BaseType, Expression, InfixMatMul, call, call_on, select_expression
 from .dtypes import lookup_dtype
 from .exceptions import DimensionMismatch
-from .operators import get_typed_op, semiring as _semiring
+from .operators import binary as _binary, get_typed_op, monoid as _monoid, semiring as _semiring
 from .vector import Vector, _name_counter, _ptr
 
 GrB_CSR_FORMAT, GrB_CSC_FORMAT = 0, 1
@@ -319,6 +319,16 @@ class Matrix(BaseType):
         """``C << A.mxm(B, semiring)``  (reference core/matrix.py:2264-2331 -> C ``GrB_mxm``)."""
         return _mxm(self, other, op)
 
+    def ewise_add(self, other, op=_monoid.plus):
+        """``C << A.ewise_add(B, op)``: union of the patterns; ``op`` where both have an entry (reference core/matrix.py
+        ewise_add -> C ``GrB_Matrix_eWiseAdd_<opclass>``)."""
+        return _ewise(self, other, op, "ewise_add", "GrB_Matrix_eWiseAdd")
+
+    def ewise_mult(self, other, op=_binary.times):
+        """``C << A.ewise_mult(B, op)``: intersection of the patterns (reference core/matrix.py ewise_mult -> C
+        ``GrB_Matrix_eWiseMult_<opclass>``)."""
+        return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
+
     def reduce_rowwise(self, op="plus"):
         return _reduce_vector(self, op, "reduce_rowwise", False)
 
@@ -369,6 +379,16 @@ class TransposedMatrix:
 
     def mxm(self, other, op=_semiring.plus_times):
         return _mxm(self, other, op)
+
+    def ewise_add(self, other, op=_monoid.plus):
+        """``C << A.ewise_add(B, op)``: union of the patterns; ``op`` where both have an entry (reference core/matrix.py
+        ewise_add -> C ``GrB_Matrix_eWiseAdd_<opclass>``)."""
+        return _ewise(self, other, op, "ewise_add", "GrB_Matrix_eWiseAdd")
+
+    def ewise_mult(self, other, op=_binary.times):
+        """``C << A.ewise_mult(B, op)``: intersection of the patterns (reference core/matrix.py ewise_mult -> C
+        ``GrB_Matrix_eWiseMult_<opclass>``)."""
+        return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
 
     def reduce_rowwise(self, op="plus"):
         return _reduce_vector(self, op, "reduce_rowwise", False)
@@ -541,6 +561,17 @@ def _mxv(A, v, op):
     expr = Expression("mxv", "GrB_mxv", [A._matrix, v], op=op, output_type=Vector, shape=(A._nrows,),
                       at=A._is_transposed)
     if A._ncols != v._size:
+        expr._force_library_error()
+    return expr
+
+
+def _ewise(A, B, op, method_name, cfunc):
+    if not isinstance(B, (Matrix, TransposedMatrix)):
+        raise TypeError(f"Expected type: Matrix; got {type(B).__name__}")
+    op = get_typed_op(op, A.dtype, B.dtype, kind="binary")
+    expr = Expression(method_name, f"{cfunc}_{op.opclass}", [A._matrix, B._matrix], op=op, output_type=Matrix, shape=A.shape,
+                      at=A._is_transposed, bt=B._is_transposed)
+    if A.shape != B.shape:
         expr._force_library_error()
     return expr
 
