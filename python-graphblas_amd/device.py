@@ -152,6 +152,13 @@ def last_stats():
     return {k: getattr(s, k) for k, _ in s._fields_}
 
 
+def matrix_cache_bytes(A):
+    """Bytes of the layouts the library has cached for ``A`` so far (GrX_Matrix_cache_bytes)."""
+    b = ctypes.c_uint64()
+    call_on(A, "GrX_Matrix_cache_bytes", [A._handle, ctypes.byref(b)])
+    return int(b.value)
+
+
 def matrix_hint_ranked(A, ranked=True):
     """The labels of ``A`` are popularity ranks already (column 0 the most referred-to, heavy rows first): the library builds its
     popularity-ordered layouts in the caller's own index order -- no permutation, no vector conversion, any shape (GrX_Matrix_hint_ranked).
