@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 
@@ -203,13 +204,26 @@ void preload_prim();
 void preload_select();
 
 template <typename T>
-struct DevPtr {  // owner of a device block that a callee allocated (freed unless released)
+struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)
     T *p = nullptr;
     DevPtr() = default;
     explicit DevPtr(T *q) : p(q) {}
     DevPtr(const DevPtr &) = delete;
     DevPtr &operator=(const DevPtr &) = delete;
+    DevPtr(DevPtr &&o) noexcept : p(o.release()) {}
+    DevPtr &operator=(DevPtr &&o) noexcept
+    {
+        if (this != &o) reset(o.release());
+        return *this;
+    }
     ~DevPtr() { dev_free(p); }
+    void reset(T *q = nullptr)
+    {
+        dev_free(p);
+        p = q;
+    }
+    T *get() const { return p; }
+    operator T *() const { return p; }
     T *release()
     {
         T *q = p;
@@ -296,152 +310,204 @@ struct GB_Vector_opaque {
     std::string err;
 };
 
+struct GB_Matrix_opaque;
+namespace grb {
+void matrix_free(GB_Matrix_opaque *A);
+struct MatrixDeleter {
+    void operator()(GB_Matrix_opaque *A) const { matrix_free(A); }
+};
+}  // namespace grb
+
+// The matrix object: what DESCRIBES the matrix (type, shape, CSR arrays, the hints `ranked` / `tr_of` / `hot_identity`, the cached transpose) as plain
+// members, and what the pull SpMV CACHES with it as one struct per layout (grb_mxv.hip builds them).  Every device array of a layout is a DevPtr member
+// and every counter / flag has a default, so `group = {}` frees the layout and returns it to "not analysed"; a builder fills a local instance and moves
+// it into the matrix as its last step, so a throw half-way leaves the matrix as it was.
 struct GB_Matrix_opaque {
+    // merge-path tile table for the pull SpMV, built on first use (ensure_tile_table)
+    struct TileTable {
+        grb::DevPtr<int64_t> d_tile_row;
+        int64_t n_tiles = 0;
+        int tile_items = 0;
+        uint64_t bytes() const { return d_tile_row ? 8ull * (uint64_t)(n_tiles + 1) : 0; }
+    };
+    // hot-column table for the pull SpMV (ensure_hot): the K most referenced columns are renumbered
+    // 0..K-1 (their x entries are gathered into a small L2-resident table per call), all others K+col
+    struct HotCols {
+        grb::DevPtr<int32_t> d_col_hot;   // nvals re-coded column indices, or nullptr.  ALWAYS nullptr on an ordered twin, whose d_col holds the codes: read through col_hot()
+        grb::DevPtr<int32_t> d_hot_cols;  // K original column indices, hottest first
+        int64_t hot_k = 0;
+        int hot_state = 0;                // 0 = not analysed, 1 = enabled, -1 = not worth it
+        bool hot_cols_dropped = false;    // the re-coded columns were released after the split was built from them (ensure_split)
+        uint64_t bytes() const { return d_hot_cols ? 4ull * (uint64_t)hot_k : 0; }  // (the table; the re-coded columns are counted by GrX_Matrix_cache_bytes)
+    };
+    // value dictionary (ensure_vdict, grb_mxv_vdict.inc): when the matrix holds at most 256 distinct values of a 4-byte type, the hot strips' lane
+    // records are [8 LDS slots as u16 | 8 value codes as u8] = 24 bytes and the kernels look the values up (LDS / L1) -- exact, whatever the values
+    // are, and half the bytes of the stream the hot strips are bound by.  (The tagged row groups and the sorted row tiles of such a matrix carry the
+    // one-byte codes too: d_tg_val / d_rt_val are then byte arrays.)  It survives a rebuild of the split; ensure_vdict replaces it.
+    struct ValueDict {
+        grb::DevPtr<void> d_vdict;         // 256 values of the matrix type (unused codes: 0)
+        int vdict_n = 0;                   // distinct values found (0: no dictionary)
+        double vals_absmax = 0.0;          // ... and the largest magnitude among them
+        bool vals_finite = false;          // every stored value is finite (known from the dictionary's scan): lets a sparse operand of a min_plus /
+                                           // max_plus product be run as a full one with +-inf under its absent entries (mxv_core)
+        grb::DevPtr<unsigned long long> d_vd_table;  // the hash table value -> slot the codes were assigned from (build time: placement kernels)
+        grb::DevPtr<unsigned char> d_vd_codes;       // code of every slot
+    };
+    // ---- the layouts derived from the long / short row split; they live in RowSplit and go with it
+    // long rows as flat class strips (k_mxv_strip, split kind 2): d_lcol / d_lval hold the entries of class c in chunks [strip_cb[c], strip_cb[c+1]) of
+    // 512 entries, sorted by (sub-range, row); segments start at multiples of 8 entries
+    struct Strips {
+        grb::DevPtr<unsigned long long> d_sstart;  // per chunk: bit l = a segment starts at lane l's 8 entries
+        grb::DevPtr<int32_t> d_sslot;      // per lane (8 entries): accumulator slot (index into d_long_rows), -1 = padding
+        grb::DevPtr<uint16_t> d_sslot16;   // (Context::strip_slot16) per lane: slot - d_sslot_base[chunk], 0xffff = padding; then d_sslot is released
+        grb::DevPtr<int32_t> d_sslot_base; // ... per chunk of 64 lanes: its smallest slot
+        int64_t strip_cb[161] = {0};       // (+ the hub level's classes behind the first strip_ncls, see hub_ncls)
+        int strip_ncls = 8;
+        // ... a matrix in its popularity order deals the entries of its HUB rows (>= hub_min_len entries) to hub_ncls = 64 classes instead of
+        // 16: four times the LDS-resident codes (2.5 Mi: 95 % of the references of an R-MAT graph instead of 81 %) at segments that are still
+        // long enough for the 8-entry lane records.  Their strips are the classes [strip_ncls, strip_ncls + hub_ncls) of strip_cb, run by a
+        // second launch of the strip kernel
+        int hub_ncls = 0;                  // 0: no hub level
+        int hub_lds_lim = 0;               // codes below it are LDS-resident in the hub level's classes
+        grb::DevPtr<int32_t> d_wg_tab;     // workgroup table of the one-launch form of k_mxv_hstrip over both levels (PullArgs::wg_tab), wg_tab_g workgroups
+        grb::DevPtr<int64_t> d_strip_cb;   // device copy of strip_cb
+        int wg_tab_g = 0;
+        int64_t strip_nseg = 0;
+        // ... or as HOT / COLD strips (split kind 4; grb_mxv_strip.inc): the entries whose column code is LDS-resident in its class live in
+        // d_hrec -- per lane of 8 entries one record [8 LDS slots as u16 (u32 for BOOL) | 8 values (or value codes)] -- in chunks
+        // [strip_cb[c], strip_cb[c+1]) of the hot classes; all other entries are the cold tiles; d_sstart / d_sslot cover the hot chunks
+        grb::DevPtr<char> d_hrec;
+        int hrec_bytes = 0;                // bytes of one lane record
+        uint64_t hot_bytes() const;        // (grb_mxv.hip)
+    };
+    // the cold entries of the long rows as tagged tiles (k_mxv_ctile, grb_mxv_ctile.inc): sorted by (column range, long row), a tile holds entries
+    // [tiles[t].u0 * 4, ... + 4 n_units): column code, value, 16-bit row in the tile
+    struct ColdTiles {
+        grb::DevPtr<int32_t> d_ct_col;
+        grb::DevPtr<void> d_ct_val;        // nullptr for iso matrices
+        grb::DevPtr<uint16_t> d_ct_loc;
+        grb::DevPtr<void> d_ct_tiles;      // CTile[ct_ntiles] (+ packed: the tiles' range bases)
+        grb::DevPtr<int32_t> d_ct_order;   // tile numbers in the order the XCDs walk them: XCD x takes d_ct_order[ct_xoff[x] .. ct_xoff[x + 1])
+        int64_t ct_xoff[9] = {0};
+        int64_t ct_ntiles = 0;
+        int64_t ct_units = 0;
+        int ct_mode = 0;                   // (Context::ctile_pack) 0: d_ct_col / d_ct_val / d_ct_loc as three streams; 1: d_ct_col holds slot << 19 | (column - base of
+                                           // the tile's column range), no d_ct_loc, the tiles' range bases behind the CTile array; 2: ... and d_ct_val holds one-byte codes
+        uint64_t bytes(uint64_t vs) const; // (grb_mxv.hip)
+    };
+    // the short rows as tagged row groups (k_mxv_rows_tag; short_kernel = 5): per group of 64 rows its entries contiguous, padded to a
+    // multiple of 4, one byte per entry naming its row inside the group (64 = padding)
+    struct TaggedGroups {
+        grb::DevPtr<int32_t> d_tg_off;       // per group (+1): first entry / 4
+        grb::DevPtr<int32_t> d_tg_col;
+        grb::DevPtr<void> d_tg_val;          // nullptr for iso matrices
+        grb::DevPtr<unsigned char> d_tg_tag;
+        grb::DevPtr<uint64_t> d_tg_nonempty; // per group: bit l = short row 64 g + l has an entry
+        int64_t tg_units = 0;
+        int tg_state = 0;  // 0 nothing, 2 offsets + non-empty words (ensure_tagged_index), 1 + the entries (ensure_tagged)
+        uint64_t bytes(uint64_t nrows, uint64_t vs, bool dict) const;  // (grb_mxv.hip)
+    };
+    // ... and an ordered twin's short rows a second time as SORTED ROW TILES (k_mxv_rtile, grb_mxv_rtile.inc): tiles of up to rt_rows4 rows
+    // (8-byte accumulators: half) and ~rtile_entries entries, the entries of a tile sorted by column code in lane-transposed blocks of 256:
+    // column code, 16-bit row inside the tile, value (one-byte code with a dictionary)
+    struct RowTiles {
+        grb::DevPtr<int32_t> d_rt_col;
+        grb::DevPtr<uint16_t> d_rt_tag;
+        grb::DevPtr<void> d_rt_val;
+        grb::DevPtr<void> d_rt_tiles;        // RTile[rt_ntiles]
+        grb::DevPtr<int32_t> d_rt_order;     // tile numbers, heaviest first (the order they are handed out in)
+        grb::DevPtr<unsigned int> d_rt_counter;  // the hand-out counter of a call (zeroed by k_long_init)
+        int64_t rt_units = 0;
+        int rt_ntiles = 0;
+        int rt_rows4 = 0;                  // the tile height the layout was built for (rows with 4-byte accumulators)
+        int rt_state = 0;                  // 0 = not built, 1 = built, -1 = not possible (sizes)
+        uint64_t bytes(uint64_t vs, bool dict) const;  // (grb_mxv.hip)
+    };
+    // long/short row split for the pull SpMV (ensure_split): rows with >= split_min_len entries are processed by the long-row kernels from the
+    // layouts below; the remaining rows live in `short_part` (same shape, long rows empty).  Everything built from the split is a member: dropping the
+    // split drops it all
+    struct RowSplit {
+        int split_state = 0;               // 0 = not analysed, 1 = enabled, -1 = not worth it
+        bool split_hot = false;            // short_part's columns are hot-coded
+        int split_kind = 0;                // value of the long_kernel option the split was built for
+        bool short_tagged_only = false;    // the short part keeps its row pointers only: its entries live in the tagged row groups
+        int64_t tails_max_len = 0;         // > 0: long rows with fewer entries than this have their cold entries in `short_part` (Context::cold_in_rows): the
+                                           // short-row kernels add them up and MERGE the long-row accumulator into the row's result
+        std::unique_ptr<GB_Matrix_opaque, grb::MatrixDeleter> short_part;
+        int64_t n_long = 0, n_chunks = 0;
+        grb::DevPtr<uint64_t> d_long_bits;    // bit r: row r is long
+        grb::DevPtr<int32_t> d_long_rows;     // n_long row indices
+        grb::DevPtr<int32_t> d_chunk_slot;    // per chunk: index into d_long_rows
+        grb::DevPtr<int64_t> d_chunk_start;   // per chunk: first entry
+        grb::DevPtr<int32_t> d_chunk_len;     // per chunk: entries (<= PULL_CHUNK)
+        grb::DevPtr<int32_t> d_long_prefix;   // per 64-row group: number of long rows before it
+        // bottom-up probe (BOOL matrices with class items): the first probe_k column codes of every long row, k-major
+        // (d_probe[k * n_long + i]; -1 = the row has no k-th entry) -- k_long_init tests them before any item kernel runs
+        grb::DevPtr<int32_t> d_probe;
+        int probe_k = 0;
+        // the long rows' entries: class items or flat class strips (kind 4: the hot records and the cold tiles hold them instead)
+        grb::DevPtr<int32_t> d_lcol;
+        grb::DevPtr<void> d_lval;          // nullptr for iso matrices
+        int64_t long_nnz = 0;
+        int cls_lds_lim = 0;               // codes below it are stored pre-translated to LDS slots in d_lcol / d_hrec
+        // class-partitioned copy of the long rows (k_mxv_long_grp): items = at most LONG_ITEM entries of one (column class,
+        // long row), stored contiguously in d_lcol / d_lval from d_it_start[i] (multiple of 4), sorted by class, then falling length
+        grb::DevPtr<int64_t> d_it_start;
+        grb::DevPtr<int32_t> d_it_len;
+        grb::DevPtr<int32_t> d_it_slot;
+        grb::DevPtr<int64_t> d_item_begin; // device copy of item_begin
+        int64_t item_begin[9] = {0};       // items of class c are [item_begin[c], item_begin[c+1])
+        int64_t n_items = 0;
+        Strips strips;
+        ColdTiles cold;
+        TaggedGroups tagged;
+        RowTiles rtile;
+        uint64_t bytes(uint64_t nrows, uint64_t vs, bool dict) const;  // (grb_mxv.hip)
+    };
+    // ---- vertex order (grb_mxv_order.inc): a large square matrix is laid out a second time as ord = P A P' for a permutation P by falling
+    //      column count (perm); the pull kernels run on `ord` with operands kept in that order.  `ord` is a matrix object of its own whose column
+    //      indices ARE the hot codes (hot_identity): the first hot_k positions are the hot table, no image is built.  matrix_invalidate_caches
+    //      releases `perm` and `ord` by hand (a reference count, a matrix object) before it resets the group
+    struct VertexOrder {
+        GB_Perm *perm = nullptr;           // the order of this matrix's vertex space (shared with its transpose and with vectors)
+        bool col_order_only = false;       // (GrX_Matrix_shard_setup) `perm` orders the COLUMN space only: the matrix is a row block of a sharded
+                                           // graph (m rows over n columns), its twin keeps the rows as they are and renames the columns; only the
+                                           // operand of a product carries the order, outputs and masks (m elements) stay natural
+        GB_Matrix_opaque *ord = nullptr;   // the matrix in that order (owned): layouts only -- its CSR arrays are released once they are built
+        int ord_state = 0;                 // 0 = not analysed, 1 = `ord` is built, -1 = not worth it / not possible
+        uint64_t ord_sig = 0;              // the layout options `ord` was built under
+        // (on an `ord` twin, set by ensure_ordered BEFORE its split is built -- they are no part of the split and survive its rebuild)
+        int64_t ord_live_rows = 0;         // rows at and behind this position are empty
+        grb::DevPtr<int32_t> d_cold_bounds;  // first code of every column range of the cold tiles (ct_ncr + 1 values)
+        int ct_ncr = 0;
+    };
+
     uint64_t magic;
     GrB_Type type;
     uint64_t nrows, ncols;
-    int64_t nvals;
-    int64_t *d_ptr;  // nrows+1 (nullptr while empty)
-    int32_t *d_col;
-    void *d_val;  // nvals values, or 1 value when iso
-    bool iso;
-    bool owns;             // false for adopted (GrX import, copy=0) buffers
-    GB_Matrix_opaque *tr;  // cached transpose (owned), or nullptr
-    // merge-path tile table for the pull SpMV (grb_mxv.hip), built on first use
-    int64_t *d_tile_row;
-    int64_t n_tiles;
-    int tile_items;
-    // hot-column table for the pull SpMV (grb_mxv.hip): the K most referenced columns are renumbered
-    // 0..K-1 (their x entries are gathered into a small L2-resident table per call), all others K+col
-    int32_t *d_col_hot;   // nvals re-coded column indices, or nullptr
-    int32_t *d_hot_cols;  // K original column indices, hottest first
-    int64_t hot_k;
-    int hot_state;        // 0 = not analysed, 1 = enabled, -1 = not worth it
-    bool hot_cols_dropped = false;  // d_col_hot was released after the split was built from it (ensure_split)
-    // long/short row split for the pull SpMV (grb_mxv.hip): rows with >= split_min_len entries are processed by a
-    // lean wavefront-per-chunk kernel straight from this matrix's arrays; the remaining rows live in `short_part`
-    // (same shape, long rows empty) and go through the merge-path kernel
-    GB_Matrix_opaque *short_part;
-    uint64_t *d_long_bits;    // bit r: row r is long
-    int32_t *d_long_rows;     // n_long row indices
-    int32_t *d_chunk_slot;    // per chunk: index into d_long_rows
-    int64_t *d_chunk_start;   // per chunk: first entry
-    int32_t *d_chunk_len;     // per chunk: entries (<= PULL_CHUNK)
-    int32_t *d_long_prefix;   // per 64-row group: number of long rows before it
-    // class-partitioned copy of the long rows (k_mxv_long_grp): items = at most LONG_ITEM entries of one (column class,
-    // long row), stored contiguously in d_lcol / d_lval from d_it_start[i] (multiple of 4), sorted by class, then falling length
-    int32_t *d_lcol;
-    void *d_lval;             // nullptr for iso matrices
-    int64_t *d_it_start;
-    int32_t *d_it_len;
-    int32_t *d_it_slot;
-    int64_t *d_item_begin;    // device copy of item_begin
-    int64_t item_begin[9];    // items of class c are [item_begin[c], item_begin[c+1])
-    int64_t n_items;
-    int64_t long_nnz;
-    int cls_lds_lim;          // codes below it are stored pre-translated to LDS slots in d_lcol
-    // ... or as flat class strips (k_mxv_strip, long_kernel = 2): d_lcol / d_lval hold the entries of class c in chunks
-    // [strip_cb[c], strip_cb[c+1]) of 512 entries, sorted by (sub-range, row); segments start at multiples of 8 entries
-    unsigned long long *d_sstart = nullptr;  // per chunk: bit l = a segment starts at lane l's 8 entries
-    int32_t *d_sslot = nullptr;        // per lane (8 entries): accumulator slot (index into d_long_rows), -1 = padding
-    int64_t strip_cb[161] = {0};        // (+ the hub level's classes behind the first strip_ncls, see hub_ncls)
-    int strip_ncls = 8;
-    // ... a matrix in its popularity order deals the entries of its HUB rows (>= hub_min_len entries) to hub_ncls = 64 classes instead of
-    // 16: four times the LDS-resident codes (2.5 Mi: 95 % of the references of an R-MAT graph instead of 81 %) at segments that are still
-    // long enough for the 8-entry lane records.  Their strips are the classes [strip_ncls, strip_ncls + hub_ncls) of strip_cb, run by a
-    // second launch of the strip kernel
-    int hub_ncls = 0;                  // 0: no hub level
-    int hub_lds_lim = 0;               // codes below it are LDS-resident in the hub level's classes
-    int32_t *d_wg_tab = nullptr;       // workgroup table of the one-launch form of k_mxv_hstrip over both levels (PullArgs::wg_tab), wg_tab_g workgroups
-    int64_t *d_strip_cb = nullptr;     // device copy of strip_cb
-    int wg_tab_g = 0;
-    int64_t strip_nseg = 0;
-    // ... or as HOT / COLD strips (long_kernel = 4, split kind 3; grb_mxv_strip.inc): the entries whose column code is LDS-resident in
-    // its class live in d_hrec -- per lane of 8 entries one record [8 LDS slots as u16 (u32 for BOOL) | 8 values] -- in chunks
-    // [strip_cb[c], strip_cb[c+1]) of the hot classes; all other entries (gathered from the operand image) in d_lcol / d_lval as
-    // strips of `strip_cold_ncls` contiguous column ranges, chunks [cold_cb[c], cold_cb[c+1]) in the same chunk numbering
-    // (d_lcol[0] is the first entry of chunk cold_cb[0]); d_sstart / d_sslot cover both
-    char *d_hrec = nullptr;
-    int hrec_bytes = 0;                // bytes of one lane record
-    // ... with the values DICTIONARY-CODED when the matrix holds at most 256 distinct ones (4-byte types; grb_mxv_vdict.inc): a lane
-    // record is [8 LDS slots as u16 | 8 value codes as u8] = 24 bytes, the kernels look the values up (LDS / L1) -- exact, whatever the
-    // values are, and half the bytes of the stream the hot strips are bound by
-    void *d_vdict = nullptr;           // 256 values of the matrix type (unused codes: 0)
-    int vdict_n = 0;                   // distinct values found (0: no dictionary)
-    double vals_absmax = 0.0;          // ... and the largest magnitude among them (from the dictionary)
-    bool vals_finite = false;          // every stored value is finite (known from the dictionary's scan): lets a sparse operand of a min_plus /
-                                       // max_plus product be run as a full one with +-inf under its absent entries (mxv_core)
-    unsigned long long *d_vd_table = nullptr;  // the hash table value -> slot the codes were assigned from (build time: placement kernels)
-    unsigned char *d_vd_codes = nullptr;       // code of every slot
-    // (the cold tiles and the tagged row groups of such a matrix carry the one-byte codes too: d_ct_val / d_tg_val are then byte arrays)
-    // ... the cold entries as tagged tiles (k_mxv_ctile, grb_mxv_ctile.inc): sorted by (column range, long row), tile t = (range
-    // t / ct_nsb, rows [8192 (t % ct_nsb), ...)) holds entries [tiles[t].u0 * 4, ... + 4 n_units): column code, value, 16-bit row in the tile
-    int32_t *d_ct_col = nullptr;
-    void *d_ct_val = nullptr;          // nullptr for iso matrices
-    uint16_t *d_ct_loc = nullptr;
-    void *d_ct_tiles = nullptr;        // CTile[ct_ncr * ct_nsb]
-    int ct_nsb = 0, ct_ncr = 0;
-    int64_t ct_units = 0;
-    int split_kind = 0;                // value of the long_kernel option the split was built for
-    int pull_calls = 0;                // pull products run on this matrix since its layouts were last dropped
-    // the short rows as tagged row groups (k_mxv_rows_tag; short_kernel = 5): per group of 64 rows its entries contiguous, padded to a
-    // multiple of 4, one byte per entry naming its row inside the group (64 = padding)
-    int32_t *d_tg_off = nullptr;       // per group (+1): first entry / 4
-    int32_t *d_tg_col = nullptr;
-    void *d_tg_val = nullptr;          // nullptr for iso matrices
-    unsigned char *d_tg_tag = nullptr;
-    uint64_t *d_tg_nonempty = nullptr; // per group: bit l = short row 64 g + l has an entry
-    int64_t tg_units = 0;
-    int tg_state = 0;  // 0 nothing, 2 offsets + non-empty words (ensure_tagged_index), 1 + the entries (ensure_tagged)
-    bool short_tagged_only = false;    // the short part keeps its row pointers only: its entries live in the tagged row groups
-    // ... and, round 5, an ordered twin's short rows a second time as SORTED ROW TILES (k_mxv_rtile, grb_mxv_rtile.inc): tiles of up to
-    // rt_rows4 rows (8-byte accumulators: half) and ~rtile_entries entries, the entries of a tile sorted by column code in lane-transposed
-    // blocks of 256: column code, 16-bit row inside the tile, value (one-byte code with a dictionary)
-    int32_t *d_rt_col = nullptr;
-    uint16_t *d_rt_tag = nullptr;
-    void *d_rt_val = nullptr;
-    void *d_rt_tiles = nullptr;        // RTile[rt_ntiles]
-    int32_t *d_rt_order = nullptr;     // tile numbers, heaviest first (the order they are handed out in)
-    unsigned int *d_rt_counter = nullptr;  // the hand-out counter of a call (zeroed by k_long_init)
-    // bottom-up probe (round 5, BOOL matrices with class items): the first probe_k column codes of every long row, k-major
-    // (d_probe[k * n_long + i]; -1 = the row has no k-th entry) -- k_long_init tests them before any item kernel runs
-    int32_t *d_probe = nullptr;
-    int probe_k = 0;
-    int64_t rt_units = 0;
-    int rt_ntiles = 0;
-    int rt_rows4 = 0;                  // the tile height the layout was built for (rows with 4-byte accumulators)
-    int rt_state = 0;                  // 0 = not built, 1 = built, -1 = not possible (sizes)
-    // ---- vertex order (round 4; grb_mxv_order.inc): a large square matrix is laid out a second time as ord = P A P' for a permutation P
-    //      by falling column count (perm); the pull kernels run on `ord` with operands kept in that order.  `ord` is a matrix object of its
-    //      own whose column indices ARE the hot codes (hot_identity): the first hot_k positions are the hot table, no image is built
-    bool ranked = false;               // (GrX_Matrix_hint_ranked, round 5) the caller's labels ARE popularity ranks: column j is referred to about as often as
+    int64_t nvals = 0;
+    int64_t *d_ptr = nullptr;  // nrows+1 (nullptr while empty)
+    int32_t *d_col = nullptr;
+    void *d_val = nullptr;     // nvals values, or 1 value when iso
+    bool iso = false;
+    bool owns = true;                  // false for adopted (GrX import, copy=0) buffers
+    GB_Matrix_opaque *tr = nullptr;    // cached transpose (owned), or nullptr
+    GB_Matrix_opaque *tr_of = nullptr; // this matrix is the cached transpose of tr_of (not owned)
+    bool ranked = false;               // (GrX_Matrix_hint_ranked) the caller's labels ARE popularity ranks: column j is referred to about as often as
                                        // or more often than column j + 1, heavy rows first.  The ordered layouts are then built in the caller's own order --
                                        // no permutation, vectors stay natural -- for square and non-square matrices alike (the row blocks of a sharded run
                                        // whose graph was relabelled once, up front).  A performance hint: no result depends on it.
-    GB_Perm *perm = nullptr;           // the order of this matrix's vertex space (shared with its transpose and with vectors)
-    bool col_order_only = false;       // (GrX_Matrix_shard_setup, round 6) `perm` orders the COLUMN space only: the matrix is a row block of a sharded
-                                       // graph (m rows over n columns), its twin keeps the rows as they are and renames the columns; only the
-                                       // operand of a product carries the order, outputs and masks (m elements) stay natural
-    GB_Matrix_opaque *ord = nullptr;   // the matrix in that order (owned): layouts only -- its CSR arrays are released once they are built
-    GB_Matrix_opaque *tr_of = nullptr; // this matrix is the cached transpose of tr_of (not owned)
-    int ord_state = 0;                 // 0 = not analysed, 1 = `ord` is built, -1 = not worth it / not possible
-    uint64_t ord_sig = 0;              // the layout options `ord` was built under
-    bool hot_identity = false;         // (an `ord` twin) d_col_hot aliases d_col: codes are positions; codes >= hot_k are not offset by hot_k
-    int64_t ord_live_rows = 0;         // (an `ord` twin) rows at and behind this position are empty
-    int32_t *d_cold_bounds = nullptr;  // (an `ord` twin) first code of every column range of the cold tiles (ct_ncr + 1 values)
-    int32_t *d_ct_order = nullptr;     // (cold tiles) tile numbers in the order the XCDs walk them: XCD x takes d_ct_order[ct_xoff[x] .. ct_xoff[x + 1])
-    int64_t ct_xoff[9] = {0};
-    int64_t ct_ntiles = 0;
-    int64_t n_long, n_chunks;
-    int split_state;          // 0 = not analysed, 1 = enabled, -1 = not worth it
-    bool split_hot;           // short_part's columns are hot-coded
+    bool hot_identity = false;         // (an `ord` twin) d_col holds the hot codes: codes are positions; codes >= hot_k are not offset by hot_k
+    int pull_calls = 0;                // pull products run on this matrix since its layouts were last dropped
     std::string err;
-    int ct_mode = 0;                   // (round 6, Context::ctile_pack) 0: d_ct_col / d_ct_val / d_ct_loc as three streams; 1: d_ct_col holds slot << 19 | (column - base of
-                                       // the tile's column range), no d_ct_loc, the tiles' range bases behind the CTile array; 2: ... and d_ct_val holds one-byte codes
-    uint16_t *d_sslot16 = nullptr;     // (round 6, Context::strip_slot16) per lane: slot - d_sslot_base[chunk], 0xffff = padding; then d_sslot is released
-    int32_t *d_sslot_base = nullptr;   // ... per chunk of 64 lanes: its smallest slot
-    int64_t tails_max_len = 0;         // > 0: long rows with fewer entries than this have their cold entries in `short_part` (Context::cold_in_rows): the
-                                       // short-row kernels add them up and MERGE the long-row accumulator into the row's result
+    // the cached layouts (dropped by matrix_invalidate_caches)
+    TileTable tile;
+    HotCols hot;
+    ValueDict vd;
+    RowSplit split;
+    VertexOrder order;
+    // the column array in the hot coding: the re-coded copy, or -- an ordered twin -- the matrix's own (never owned through this view)
+    const int32_t *col_hot() const { return hot_identity ? d_col : hot.d_col_hot.get(); }
 };
 
 namespace grb {

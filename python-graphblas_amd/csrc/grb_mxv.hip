@@ -66,12 +66,12 @@ static int64_t hot_table_size(int64_t n, size_t value_bytes)
 
 static void ensure_hot(GB_Matrix_opaque *A, size_t value_bytes)
 {
-    if (A->hot_state != 0) return;
-    A->hot_state = -1;
+    if (A->hot.hot_state != 0) return;
+    auto declined = [&]() { A->hot.hot_state = -1; };  // analysed, not worth it
     const int64_t n = (int64_t)A->ncols, nnz = A->nvals;
-    if (n < ctx().hot_min_cols || nnz == 0 || n + (int64_t)(1 << 22) > 0x7fffffff) return;
+    if (n < ctx().hot_min_cols || nnz == 0 || n + (int64_t)(1 << 22) > 0x7fffffff) return declined();
     const int64_t k = hot_table_size(n, value_bytes);
-    if (k < 64) return;
+    if (k < 64) return declined();
     DevBuf<unsigned int> cnt(n, true);
     const int hstride = nnz >= ((int64_t)1 << 26) ? 8 : 1;
     hipLaunchKernelGGL(k_hot_hist, dim3((unsigned)ceil_div(nnz, 256 * hstride)), dim3(256), 0, ctx().stream, A->d_col, nnz, cnt.p, hstride);
@@ -81,22 +81,20 @@ static void ensure_hot(GB_Matrix_opaque *A, size_t value_bytes)
     prim_sort_pairs_u64_u32(keys.p, keys2.p, ids.p, ids2.p, n, 32);
     DevBuf<int32_t> rank(n);
     GRB_HIP(hipMemsetAsync(rank.p, 0xff, sizeof(int32_t) * (size_t)n, ctx().stream));
-    int32_t *hot_cols = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)k);
+    GB_Matrix_opaque::HotCols hc;
+    hc.d_hot_cols.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)k));
     DevBuf<unsigned long long> covered(1, true);
     hipLaunchKernelGGL(k_hot_rank, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, ctx().stream, ids2.p, keys2.p, k, rank.p,
-                       hot_cols, covered.p);
+                       hc.d_hot_cols.get(), covered.p);
     unsigned long long cov = 0;
     d2h(&cov, covered.p, sizeof(cov));
-    if ((double)cov * hstride < 0.25 * (double)nnz) {  // flat degree distribution: the table would not pay for itself
-        dev_free(hot_cols);
-        return;
-    }
-    A->d_col_hot = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnz);
+    if ((double)cov * hstride < 0.25 * (double)nnz) return declined();  // flat degree distribution: the table would not pay for itself
+    hc.d_col_hot.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnz));
     hipLaunchKernelGGL(k_hot_recode, dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, ctx().stream, A->d_col, nnz, rank.p,
-                       (int)k, A->d_col_hot);
-    A->d_hot_cols = hot_cols;
-    A->hot_k = k;
-    A->hot_state = 1;
+                       (int)k, hc.d_col_hot.get());
+    hc.hot_k = k;
+    hc.hot_state = 1;
+    A->hot = std::move(hc);
 }
 
 // The re-coded copy of the whole column array is released once the split is built from it (ensure_split); a later rebuild of the
@@ -104,35 +102,35 @@ static void ensure_hot(GB_Matrix_opaque *A, size_t value_bytes)
 static void restore_hot_cols(GB_Matrix_opaque *A)
 {
     if (A->hot_identity) fail(GrB_PANIC, "pull SpMV: an ordered layout cannot be rebuilt in place (internal error)");
-    if (A->d_col_hot || A->hot_state != 1 || !A->d_hot_cols) return;
+    if (A->hot.d_col_hot || A->hot.hot_state != 1 || !A->hot.d_hot_cols) return;
     const int64_t n = (int64_t)A->ncols, nnz = A->nvals;
     DevBuf<int32_t> rank(n);
     GRB_HIP(hipMemsetAsync(rank.p, 0xff, sizeof(int32_t) * (size_t)n, ctx().stream));
-    hipLaunchKernelGGL(k_hot_rank_scatter, dim3((unsigned)ceil_div(A->hot_k, 256)), dim3(256), 0, ctx().stream, (const int32_t *)A->d_hot_cols,
-                       A->hot_k, rank.p);
-    A->d_col_hot = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(nnz ? nnz : 1));
+    hipLaunchKernelGGL(k_hot_rank_scatter, dim3((unsigned)ceil_div(A->hot.hot_k, 256)), dim3(256), 0, ctx().stream, (const int32_t *)A->hot.d_hot_cols,
+                       A->hot.hot_k, rank.p);
+    DevPtr<int32_t> col_hot((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(nnz ? nnz : 1)));
     hipLaunchKernelGGL(k_hot_recode, dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, ctx().stream, A->d_col, nnz, (const int32_t *)rank.p,
-                       (int)A->hot_k, A->d_col_hot);
+                       (int)A->hot.hot_k, col_hot.get());
     sync_stream();  // (rank is released at the end of this scope)
-    A->hot_cols_dropped = false;
+    A->hot.d_col_hot = std::move(col_hot);
+    A->hot.hot_cols_dropped = false;
 }
 
 template <typename T> struct PullIPT { static constexpr int value = sizeof(T) >= 8 ? 4 : 8; };
 
 static void ensure_tile_table(GB_Matrix_opaque *A, int tile_items)
 {
-    if (A->d_tile_row && A->tile_items == tile_items) return;
-    dev_free(A->d_tile_row);
-    A->d_tile_row = nullptr;
+    if (A->tile.d_tile_row && A->tile.tile_items == tile_items) return;
+    A->tile = {};
     const int64_t total = (int64_t)A->nrows + A->nvals;
-    const int64_t n_tiles = ceil_div(total, tile_items);
-    int64_t *tab = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(n_tiles + 1));
-    const int64_t nt1 = n_tiles + 1;
+    GB_Matrix_opaque::TileTable tt;
+    tt.n_tiles = ceil_div(total, tile_items);
+    tt.tile_items = tile_items;
+    tt.d_tile_row.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(tt.n_tiles + 1)));
+    const int64_t nt1 = tt.n_tiles + 1;
     hipLaunchKernelGGL(k_tile_table, dim3((unsigned)ceil_div(nt1, 256)), dim3(256), 0, ctx().stream, matrix_rowptr(A),
-                       (int64_t)A->nrows, A->nvals, tile_items, n_tiles, tab);
-    A->d_tile_row = tab;
-    A->n_tiles = n_tiles;
-    A->tile_items = tile_items;
+                       (int64_t)A->nrows, A->nvals, tile_items, tt.n_tiles, tt.d_tile_row.get());
+    A->tile = std::move(tt);
 }
 
 // diagnostics (GRB_DEBUG_FLAGS & 8): mean cycles between the phase stamps of k_mxv_pull
@@ -155,13 +153,10 @@ static void report_phase_times(const long long *d_times, int64_t n_tiles)
 }
 
 // value dictionary of a matrix (grb_mxv_vdict.inc): at most 256 distinct finite values of a 4-byte type -> one-byte codes in the lane
-// records of the hot strips, the cold tiles and the tagged row groups.  Sets A->vdict_n (0: none).
+// records of the hot strips, the cold tiles and the tagged row groups.  Sets A->vd.vdict_n (0: none).
 static void ensure_vdict(GB_Matrix_opaque *A, bool wanted)
 {
-    dev_free(A->d_vdict); dev_free(A->d_vd_table); dev_free(A->d_vd_codes);
-    A->d_vdict = nullptr; A->d_vd_table = nullptr; A->d_vd_codes = nullptr;
-    A->vdict_n = 0;
-    A->vals_finite = false;
+    A->vd = {};
     const int64_t nnz = A->nvals;
     if (!wanted || !ctx().value_dict || A->iso || A->type->size != 4 || A->type->code == TC_BOOL || nnz == 0) return;
     DevBuf<unsigned long long> vd_table(VDICT_SLOTS, true);
@@ -187,21 +182,22 @@ static void ensure_vdict(GB_Matrix_opaque *A, bool wanted)
         next++;
     }
     if (next != (int)h_count) return;
-    A->d_vdict = dev_alloc(256 * sizeof(uint32_t));
-    h2d(A->d_vdict, dict.data(), 256 * sizeof(uint32_t));
-    A->d_vd_table = (unsigned long long *)dev_alloc(sizeof(unsigned long long) * VDICT_SLOTS);
-    h2d(A->d_vd_table, h_table.data(), sizeof(unsigned long long) * VDICT_SLOTS);
-    A->d_vd_codes = (unsigned char *)dev_alloc(VDICT_SLOTS);
-    h2d(A->d_vd_codes, h_codes.data(), VDICT_SLOTS);
-    A->vdict_n = next;
-    A->vals_finite = true;  // (every distinct value was looked at above)
-    A->vals_absmax = 0.0;
+    GB_Matrix_opaque::ValueDict vd;
+    vd.d_vdict.reset(dev_alloc(256 * sizeof(uint32_t)));
+    h2d(vd.d_vdict, dict.data(), 256 * sizeof(uint32_t));
+    vd.d_vd_table.reset((unsigned long long *)dev_alloc(sizeof(unsigned long long) * VDICT_SLOTS));
+    h2d(vd.d_vd_table, h_table.data(), sizeof(unsigned long long) * VDICT_SLOTS);
+    vd.d_vd_codes.reset((unsigned char *)dev_alloc(VDICT_SLOTS));
+    h2d(vd.d_vd_codes, h_codes.data(), VDICT_SLOTS);
+    vd.vdict_n = next;
+    vd.vals_finite = true;  // (every distinct value was looked at above)
     if (A->type->code == TC_FP32)
         for (int i = 0; i < next; i++) {
             float f;
             memcpy(&f, &dict[(size_t)i], 4);
-            A->vals_absmax = std::max(A->vals_absmax, (double)(f < 0 ? -f : f));
+            vd.vals_absmax = std::max(vd.vals_absmax, (double)(f < 0 ? -f : f));
         }
+    A->vd = std::move(vd);
 }
 
 // Analyse (once) whether the rows split usefully into long and short ones and build the two parts.
@@ -229,40 +225,22 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
     // (the tagged groups number their units with 31 bits and their entries with 33: beyond that the short part keeps its CSR arrays
     //  and the row-group kernel -- the same guard as where short_tagged_only is set, or the split would be rebuilt at every call)
     const bool want_tagged_only = short_kernel_for(A) == 5 && A->nvals < 0x1ffffffffll;
-    if (A->split_state != 0 && (A->split_state < 0 || (A->split_hot == hot && A->split_kind == kind && A->short_tagged_only == want_tagged_only &&
-                                                       ((A->split_kind != 2 && A->split_kind != 4) || (A->strip_nseg == 0 && A->ct_units == 0) || A->strip_ncls == ncls_opt)))) return;
-    if (A->split_state == 1) {  // built against the other column coding (or for another long-row kernel): rebuild
-        matrix_free(A->short_part);
-        A->short_part = nullptr;
-        dev_free(A->d_long_bits); dev_free(A->d_long_rows); dev_free(A->d_chunk_slot); dev_free(A->d_chunk_start); dev_free(A->d_chunk_len); dev_free(A->d_long_prefix);
-        dev_free(A->d_probe); A->d_probe = nullptr; A->probe_k = 0;
-        dev_free(A->d_lcol); dev_free(A->d_lval); dev_free(A->d_it_start); dev_free(A->d_it_len); dev_free(A->d_it_slot);
-        dev_free(A->d_item_begin);
-        // (layouts derived from the short part go with it)
-        dev_free(A->d_tg_off); dev_free(A->d_tg_col); dev_free(A->d_tg_val); dev_free(A->d_tg_tag); dev_free(A->d_tg_nonempty);
-        A->d_tg_off = nullptr; A->d_tg_col = nullptr; A->d_tg_val = nullptr; A->d_tg_tag = nullptr; A->d_tg_nonempty = nullptr; A->tg_state = 0;
-        dev_free(A->d_rt_col); dev_free(A->d_rt_tag); dev_free(A->d_rt_val); dev_free(A->d_rt_tiles); dev_free(A->d_rt_order); dev_free(A->d_rt_counter);
-        A->d_rt_col = nullptr; A->d_rt_tag = nullptr; A->d_rt_val = nullptr; A->d_rt_tiles = nullptr; A->d_rt_order = nullptr; A->d_rt_counter = nullptr;
-        A->rt_state = 0; A->rt_units = 0; A->rt_ntiles = 0;
-        A->tails_max_len = 0;
-        dev_free(A->d_sstart); dev_free(A->d_sslot); dev_free(A->d_hrec); dev_free(A->d_sslot16); dev_free(A->d_sslot_base);
-        A->d_sstart = nullptr; A->d_sslot = nullptr; A->d_hrec = nullptr; A->strip_nseg = 0; A->hub_ncls = 0;
-        A->d_sslot16 = nullptr; A->d_sslot_base = nullptr;
-        dev_free(A->d_ct_col); dev_free(A->d_ct_val); dev_free(A->d_ct_loc); dev_free(A->d_ct_tiles); dev_free(A->d_ct_order);
-        A->d_ct_col = nullptr; A->d_ct_val = nullptr; A->d_ct_loc = nullptr; A->d_ct_tiles = nullptr; A->d_ct_order = nullptr; A->ct_units = 0; A->ct_ntiles = 0;
-        A->d_lcol = nullptr; A->d_lval = nullptr; A->d_it_start = nullptr; A->d_it_len = nullptr; A->d_it_slot = nullptr;
-        A->d_item_begin = nullptr; A->long_nnz = 0; A->n_items = 0;
-        A->d_long_prefix = nullptr;
-        A->d_long_bits = nullptr; A->d_long_rows = nullptr; A->d_chunk_slot = nullptr; A->d_chunk_start = nullptr; A->d_chunk_len = nullptr;
-    }
-    A->split_state = -1;
-    if (hot && A->hot_cols_dropped) {  // (a rebuild in the hot coding after the re-coded columns were released)
+    if (A->split.split_state != 0 && (A->split.split_state < 0 || (A->split.split_hot == hot && A->split.split_kind == kind && A->split.short_tagged_only == want_tagged_only &&
+                                                       ((A->split.split_kind != 2 && A->split.split_kind != 4) || (A->split.strips.strip_nseg == 0 && A->split.cold.ct_units == 0) || A->split.strips.strip_ncls == ncls_opt)))) return;
+    // built against the other column coding (or for another long-row kernel): rebuild -- the short part and every layout derived from the split go
+    // with it (the dictionary and, on a twin, the column ranges of its cold tiles are no part of it)
+    A->split = {};
+    auto declined = [&]() {  // analysed, not worth it
+        A->split = {};
+        A->split.split_state = -1;
+    };
+    if (hot && A->hot.hot_cols_dropped) {  // (a rebuild in the hot coding after the re-coded columns were released)
         restore_hot_cols(A);
-        col_src = A->d_col_hot;
+        col_src = A->hot.d_col_hot;
     }
     if (!col_src) fail(GrB_PANIC, "pull SpMV: the split cannot be built without a column source (internal error)");
     const int64_t m = (int64_t)A->nrows, nnz = A->nvals;
-    if (nnz < ctx().split_min_nnz || m == 0 || (ctx().debug_flags & 128)) return;
+    if (nnz < ctx().split_min_nnz || m == 0 || (ctx().debug_flags & 128)) return declined();
     const int min_len = ctx().split_min_len > 0 ? ctx().split_min_len : ((kind == 2 || kind == 4) ? 64 : 256);  // (measured optima, scripts/gpu_r02_nc.sh)
     // Round 6: the COLD entries of the long rows below `tail_max` entries -- column codes that are not LDS-resident in their class: codes from
     // `tail_lim` on -- join the short part (Context::cold_in_rows): on an ordered twin the short rows' sorted row tiles stream them at 7 bytes
@@ -272,9 +250,9 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
     int64_t tail_max = 0;
     unsigned tail_lim = 0u;
     if (kind == 4 && A->hot_identity && hot && want_tagged_only && ctx().rows_tile && ctx().cold_in_rows > min_len && nnz < 0xf0000000ll &&
-        A->d_cold_bounds && A->ct_ncr > 0 && !A->iso && (A->type->size == 4 || A->type->size == 8)) {
+        A->order.d_cold_bounds && A->order.ct_ncr > 0 && !A->iso && (A->type->size == 4 || A->type->size == 8)) {
         const int ncls_t = (ctx().long_classes == 16 || ctx().long_classes == 32 || ctx().long_classes == 64) ? ctx().long_classes : 8;
-        const int64_t lim_t = std::min<int64_t>(A->hot_k, long_lds_codes((int)A->type->size, false, LONG_LDS_WORDS) / 8 * ncls_t);
+        const int64_t lim_t = std::min<int64_t>(A->hot.hot_k, long_lds_codes((int)A->type->size, false, LONG_LDS_WORDS) / 8 * ncls_t);
         const bool hub_t = ctx().hub_min_len > 0 && ncls_t < 64;
         tail_max = hub_t ? std::min<int64_t>(ctx().cold_in_rows, ctx().hub_min_len) : (int64_t)ctx().cold_in_rows;
         tail_lim = (unsigned)lim_t;
@@ -294,40 +272,40 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
     d2h(&nc, nchunk.p + m, 8);
     unsigned long long n_tails = 0;
     if (tail_max > 0) d2h(&n_tails, tails_total.p, 8);
-    if (nl == 0 || (double)(nnz - nnz_short + (int64_t)n_tails) < 0.3 * (double)nnz) return;  // too few entries in long rows to pay off
+    if (nl == 0 || (double)(nnz - nnz_short + (int64_t)n_tails) < 0.3 * (double)nnz) return declined();  // too few entries in long rows to pay off
     ensure_vdict(A, kind == 4);
-    GB_Matrix_opaque *S = matrix_new(A->type, A->nrows, A->ncols);
-    try {
+    // the split is built here and moved into the matrix when it is complete: a throw on the way releases it and leaves A without a split
+    GB_Matrix_opaque::RowSplit sp;
+    sp.short_part.reset(matrix_new(A->type, A->nrows, A->ncols));
+    GB_Matrix_opaque *S = sp.short_part.get();
+    {
         S->d_ptr = slen.release();
         S->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(nnz_short ? nnz_short : 1));
         S->d_val = dev_alloc(A->type->size * (size_t)(A->iso ? 1 : (nnz_short ? nnz_short : 1)));
         if (A->iso) d2d(S->d_val, A->d_val, A->type->size);
         S->iso = A->iso;
         S->nvals = nnz_short;
-        A->d_long_rows = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nl);
-        A->d_chunk_slot = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nc);
-        A->d_chunk_start = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)nc);
-        A->d_chunk_len = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nc);
-        A->d_long_prefix = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)bits_words64((uint64_t)m));
+        sp.d_long_rows.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nl));
+        sp.d_chunk_slot.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nc));
+        sp.d_chunk_start.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)nc));
+        sp.d_chunk_len.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nc));
+        sp.d_long_prefix.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)bits_words64((uint64_t)m)));
         GRB_DISPATCH_TYPE(A->type->code, T, {
             hipLaunchKernelGGL((k_split_fill<T>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream,
                                (const int64_t *)A->d_ptr, col_src, (const T *)A->d_val, A->iso ? 1 : 0, m, min_len,
                                (const int64_t *)S->d_ptr, (const int64_t *)lflag.p, (const int64_t *)nchunk.p, S->d_col,
-                               (T *)S->d_val, A->d_long_rows, A->d_chunk_slot, A->d_chunk_start, A->d_chunk_len, A->d_long_prefix);
+                               (T *)S->d_val, sp.d_long_rows, sp.d_chunk_slot, sp.d_chunk_start, sp.d_chunk_len, sp.d_long_prefix);
             if (tail_max > 0)
                 hipLaunchKernelGGL((k_split_fill_tails<T>), dim3((unsigned)ceil_div(nl, 4)), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr, col_src,
-                                   (const T *)A->d_val, A->iso ? 1 : 0, (const int32_t *)A->d_long_rows, nl, (const int64_t *)S->d_ptr, S->d_col, (T *)S->d_val,
+                                   (const T *)A->d_val, A->iso ? 1 : 0, (const int32_t *)sp.d_long_rows, nl, (const int64_t *)S->d_ptr, S->d_col, (T *)S->d_val,
                                    tail_max, tail_lim);
         })
         // the bottom-up probe of a BOOL matrix (k_long_init): the first 16 column codes of every long row
-        dev_free(A->d_probe);
-        A->d_probe = nullptr;
-        A->probe_k = 0;
         if (A->type->code == TC_BOOL && kind == 1 && nl * 16 < 0x7fffffffll) {
-            A->d_probe = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(nl * 16));
+            sp.d_probe.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(nl * 16)));
             hipLaunchKernelGGL(k_probe_fill, dim3((unsigned)ceil_div(nl * 16, 256)), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr, col_src,
-                               (const int32_t *)A->d_long_rows, nl, 16, A->d_probe);
-            A->probe_k = 16;
+                               (const int32_t *)sp.d_long_rows, nl, 16, sp.d_probe);
+            sp.probe_k = 16;
         }
         // class-partitioned copy of the long rows: sort the entries by (class, slot), cut the runs into items, sort the
         // items by (class, falling length), lay them out with 4-entry aligned starts
@@ -337,12 +315,10 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
         DevBuf<int64_t> lpre(tail_max > 0 ? nl + 1 : 0);
         int64_t nnz_keyed = nnz_long;
         if (tail_max > 0) {
-            hipLaunchKernelGGL(k_long_lens, dim3((unsigned)ceil_div(nl + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr, (const int32_t *)A->d_long_rows, nl, lpre.p);
+            hipLaunchKernelGGL(k_long_lens, dim3((unsigned)ceil_div(nl + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr, (const int32_t *)sp.d_long_rows, nl, lpre.p);
             prim_exclusive_sum_i64(lpre.p, lpre.p, nl + 1);
             d2h(&nnz_keyed, lpre.p + nl, 8);
         }
-        A->long_nnz = 0;
-        A->n_items = 0;
         if (nnz_keyed < 0xf0000000ll && nnz < 0xffffffffll) {
             // sub-ranges per class: sized so that one sub-range of the operand image is ~2 MiB (half an XCD's L2; BOOL images are
             // bit-packed and fit as they are); measured on R-MAT scale 24 fp32: 4 sub-ranges -3 % per call, and rows need ~512
@@ -352,8 +328,8 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                                  ? ctx().long_classes : 8;
             // hot / cold strips: the codes that are LDS-resident in their class, and the contiguous column ranges of the others
             const int COLD_CLS = 8;
-            const int64_t lds_lim4 = std::min<int64_t>(hot ? A->hot_k : 0, long_lds_codes((int)A->type->size, A->type->code == TC_BOOL, LONG_LDS_WORDS) / 8 * ncls);
-            const int64_t codes_total = (int64_t)A->ncols + ((hot && !A->hot_identity) ? A->hot_k : 0);
+            const int64_t lds_lim4 = std::min<int64_t>(hot ? A->hot.hot_k : 0, long_lds_codes((int)A->type->size, A->type->code == TC_BOOL, LONG_LDS_WORDS) / 8 * ncls);
+            const int64_t codes_total = (int64_t)A->ncols + ((hot && !A->hot_identity) ? A->hot.hot_k : 0);
             // (kind 4: the cold entries go to tagged tiles of 8 * `sub` column ranges of ~3 MiB of the operand image each, every row cut)
             const int range_cls = kind == 4 ? COLD_CLS : ncls;
             unsigned sub = 1;
@@ -369,7 +345,7 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
             DevBuf<uint64_t> keys(nnz_keyed), keys2(nnz_keyed);
             DevBuf<uint32_t> idx(nnz_keyed), idx2(nnz_keyed);
             // (a matrix in its popularity order carries its own column ranges: about equal reference counts, at most ~2 MiB of operand)
-            const bool own_ranges = kind == 4 && A->hot_identity && A->d_cold_bounds && A->ct_ncr > 0;
+            const bool own_ranges = kind == 4 && A->hot_identity && A->order.d_cold_bounds && A->order.ct_ncr > 0;
             // ... and deals its hub rows to 64 classes (GB_Matrix_opaque::hub_ncls): only there are the LDS heads lines of the operand
             // itself -- with a per-call hot table four times the codes would cost four times the image
             const int hub_ncls = (own_ranges && ctx().hub_min_len > 0 && ncls < 64) ? 64 : 0;
@@ -377,22 +353,22 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
             const int64_t hub_len = hub_ncls ? (int64_t)ctx().hub_min_len : 0;
             if (tail_max > 0 && (!own_ranges || (int64_t)tail_lim != lds_lim4 || (hub_ncls && tail_max > hub_len)))
                 fail(GrB_PANIC, "long / short split: the cold entries of the long rows were cut at another limit than the class keys use (internal error)");
-            const unsigned discard_cls = (unsigned)(ncls + hub_ncls + (own_ranges ? A->ct_ncr : COLD_CLS * (int)sub));  // (behind the last cold range)
+            const unsigned discard_cls = (unsigned)(ncls + hub_ncls + (own_ranges ? A->order.ct_ncr : COLD_CLS * (int)sub));  // (behind the last cold range)
             if (kind == 4)
                 hipLaunchKernelGGL(k_long_keys, dim3((unsigned)nl), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr,
-                                   (const int64_t *)S->d_ptr, (const int32_t *)A->d_long_rows, col_src, nl, keys.p, idx.p,
-                                   (unsigned)lds_lim4, (unsigned)std::max<int64_t>(1, ceil_div(codes_total - std::max<int64_t>(lds_lim4, hot ? A->hot_k : 0), (int64_t)COLD_CLS * (int64_t)sub)),
-                                   sub, sub_min_len, (unsigned)ncls, 2, (unsigned)(hot ? A->hot_k : 0),
-                                   own_ranges ? (const int32_t *)A->d_cold_bounds : (const int32_t *)nullptr, own_ranges ? A->ct_ncr + 1 : 0,
+                                   (const int64_t *)S->d_ptr, (const int32_t *)sp.d_long_rows, col_src, nl, keys.p, idx.p,
+                                   (unsigned)lds_lim4, (unsigned)std::max<int64_t>(1, ceil_div(codes_total - std::max<int64_t>(lds_lim4, hot ? A->hot.hot_k : 0), (int64_t)COLD_CLS * (int64_t)sub)),
+                                   sub, sub_min_len, (unsigned)ncls, 2, (unsigned)(hot ? A->hot.hot_k : 0),
+                                   own_ranges ? (const int32_t *)A->order.d_cold_bounds : (const int32_t *)nullptr, own_ranges ? A->order.ct_ncr + 1 : 0,
                                    hub_len, (unsigned)hub_lim, (unsigned)hub_ncls, tail_max, discard_cls, tail_max > 0 ? (const int64_t *)lpre.p : (const int64_t *)nullptr);
             else
             hipLaunchKernelGGL(k_long_keys, dim3((unsigned)nl), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr,
-                               (const int64_t *)S->d_ptr, (const int32_t *)A->d_long_rows, col_src, nl, keys.p, idx.p,
-                               (unsigned)(hot ? A->hot_k : 0), (unsigned)std::max<int64_t>(1, ceil_div((int64_t)A->ncols, (int64_t)ncls * (int64_t)sub)),
+                               (const int64_t *)S->d_ptr, (const int32_t *)sp.d_long_rows, col_src, nl, keys.p, idx.p,
+                               (unsigned)(hot ? A->hot.hot_k : 0), (unsigned)std::max<int64_t>(1, ceil_div((int64_t)A->ncols, (int64_t)ncls * (int64_t)sub)),
                                sub, sub_min_len, (unsigned)ncls, kind == 2 ? 1 : 0, 0u, (const int32_t *)nullptr, 0, (int64_t)0, 0u, 0u, (int64_t)0, 0u, (const int64_t *)nullptr);
             // (virtual classes: kind 2 ncls * sub; kind 4 ncls hot classes + COLD_CLS cold ranges, with `sub` = 1 in the segment tables)
             const int nvc = ncls + hub_ncls;                                            // classes of the strips (chunk ranges)
-            const int n_cr = own_ranges ? A->ct_ncr : COLD_CLS * (int)sub;             // kind 4: column ranges of the cold tiles
+            const int n_cr = own_ranges ? A->order.ct_ncr : COLD_CLS * (int)sub;             // kind 4: column ranges of the cold tiles
             const int nvirt = kind == 4 ? nvc + n_cr + (tail_max > 0 ? 1 : 0) : ncls * (int)sub;  // virtual classes (sort keys; + the discard class)
             const int hot_cls = 0;
             const unsigned strip_sub = kind == 4 ? 1u : sub;                            // virtual classes per strip class
@@ -410,11 +386,11 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
             int ct_mode = 0;
             std::vector<int32_t> h_bounds;
             if (kind == 4 && own_ranges && ctx().ctile_pack > 0) {
-                h_bounds.resize((size_t)A->ct_ncr + 1);
-                d2h(h_bounds.data(), A->d_cold_bounds, sizeof(int32_t) * h_bounds.size());
+                h_bounds.resize((size_t)A->order.ct_ncr + 1);
+                d2h(h_bounds.data(), A->order.d_cold_bounds, sizeof(int32_t) * h_bounds.size());
                 int64_t widest = 0;
-                for (int r = 0; r < A->ct_ncr; r++) widest = std::max<int64_t>(widest, (int64_t)h_bounds[(size_t)r + 1] - (int64_t)h_bounds[(size_t)r]);
-                if (widest < ((int64_t)1 << 19) - 1) ct_mode = (ctx().ctile_pack == 2 && A->vdict_n > 0 && A->type->size == 4 && !A->iso) ? 2 : 1;
+                for (int r = 0; r < A->order.ct_ncr; r++) widest = std::max<int64_t>(widest, (int64_t)h_bounds[(size_t)r + 1] - (int64_t)h_bounds[(size_t)r]);
+                if (widest < ((int64_t)1 << 19) - 1) ct_mode = (ctx().ctile_pack == 2 && A->vd.vdict_n > 0 && A->type->size == 4 && !A->iso) ? 2 : 1;
             }
             const int ct_slots = ct_mode ? CT_PACK_SLOTS : (A->type->size > 4 ? CT_SLOTS / 2 : CT_SLOTS);  // (CtSlots<W>: 8-byte accumulators take half the slots)
             const int n_sb = (int)ceil_div(nl, (int64_t)ct_slots);
@@ -432,13 +408,12 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                     fail(GrB_PANIC, "long / short split: the short part and the class keys disagree about the cold entries that moved (internal error)");
             }
             if (kind == 4) {
-                A->long_nnz = nnz_long;
-                A->strip_ncls = ncls;
-                A->hub_ncls = hub_ncls;
-                A->hub_lds_lim = (int)hub_lim;
-                A->strip_nseg = 0;
-                A->cls_lds_lim = (int)lds_lim4;
-                for (int c = 0; c <= nvc; c++) A->strip_cb[c] = 0;
+                sp.long_nnz = nnz_long;
+                sp.strips.strip_ncls = ncls;
+                sp.strips.hub_ncls = hub_ncls;
+                sp.strips.hub_lds_lim = (int)hub_lim;
+                sp.cls_lds_lim = (int)lds_lim4;
+                for (int c = 0; c <= nvc; c++) sp.strips.strip_cb[c] = 0;
             }
             if (strips && n_strip > 0) {
                 // flat class strips (grb_mxv_strip.inc): segments = runs of equal keys; every segment padded to a multiple of 8
@@ -471,32 +446,31 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 h_cb[nvc] = base / STRIP_CH;
                 const int64_t padded = base, nch = padded / STRIP_CH;
                 h2d(cshift.p, h_shift, sizeof(int64_t) * (size_t)nvc);
-                A->cls_lds_lim = (int)lds_lim4;
+                sp.cls_lds_lim = (int)lds_lim4;
                 const int64_t hot_chunks = kind == 4 ? h_cb[nvc] : 0;    // chunks of the hot strips (kind 4: all of them)
                 const int64_t flat_entries = kind == 4 ? 0 : padded;     // entries held by d_lcol / d_lval
                 const int code_bytes = A->type->code == TC_BOOL ? 32 : 16;
-                const bool use_dict = A->vdict_n > 0;
+                const bool use_dict = A->vd.vdict_n > 0;
                 const int val_bytes = A->iso ? 0 : (use_dict ? 8 : (int)std::max<size_t>(16, 8 * A->type->size));
                 if (padded > 0 && padded < 0x7fffffff0ll) {
-                    A->d_lcol = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(flat_entries, 1));
-                    A->d_lval = A->iso ? nullptr : dev_alloc(A->type->size * (size_t)std::max<int64_t>(flat_entries, 1));
-                    A->d_sstart = (unsigned long long *)dev_alloc(sizeof(unsigned long long) * (size_t)nch);
-                    A->d_sslot = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(padded / 8));
-                    GRB_HIP(hipMemsetAsync(A->d_sslot, 0xff, sizeof(int32_t) * (size_t)(padded / 8), ctx().stream));
-                    GRB_HIP(hipMemsetAsync(A->d_lcol, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(flat_entries, 1), ctx().stream));
-                    if (A->d_lval) GRB_HIP(hipMemsetAsync(A->d_lval, 0, A->type->size * (size_t)std::max<int64_t>(flat_entries, 1), ctx().stream));
-                    GRB_HIP(hipMemsetAsync(A->d_sstart, 0, sizeof(unsigned long long) * (size_t)nch, ctx().stream));
-                    A->hrec_bytes = 0;
+                    sp.d_lcol.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(flat_entries, 1)));
+                    sp.d_lval.reset(A->iso ? nullptr : dev_alloc(A->type->size * (size_t)std::max<int64_t>(flat_entries, 1)));
+                    sp.strips.d_sstart.reset((unsigned long long *)dev_alloc(sizeof(unsigned long long) * (size_t)nch));
+                    sp.strips.d_sslot.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(padded / 8)));
+                    GRB_HIP(hipMemsetAsync(sp.strips.d_sslot, 0xff, sizeof(int32_t) * (size_t)(padded / 8), ctx().stream));
+                    GRB_HIP(hipMemsetAsync(sp.d_lcol, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(flat_entries, 1), ctx().stream));
+                    if (sp.d_lval) GRB_HIP(hipMemsetAsync(sp.d_lval, 0, A->type->size * (size_t)std::max<int64_t>(flat_entries, 1), ctx().stream));
+                    GRB_HIP(hipMemsetAsync(sp.strips.d_sstart, 0, sizeof(unsigned long long) * (size_t)nch, ctx().stream));
                     if (kind == 4) {
-                        A->hrec_bytes = code_bytes + val_bytes;
-                        const size_t hbytes = (size_t)std::max<int64_t>(hot_chunks, 1) * 64 * (size_t)A->hrec_bytes;
-                        A->d_hrec = (char *)dev_alloc(hbytes);
-                        if (A->type->code == TC_BOOL) GRB_HIP(hipMemsetAsync(A->d_hrec, 0xff, hbytes, ctx().stream));  // (code -1 = padding)
+                        sp.strips.hrec_bytes = code_bytes + val_bytes;
+                        const size_t hbytes = (size_t)std::max<int64_t>(hot_chunks, 1) * 64 * (size_t)sp.strips.hrec_bytes;
+                        sp.strips.d_hrec.reset((char *)dev_alloc(hbytes));
+                        if (A->type->code == TC_BOOL) GRB_HIP(hipMemsetAsync(sp.strips.d_hrec, 0xff, hbytes, ctx().stream));  // (code -1 = padding)
                         else {
                             const int64_t n_rec = std::max<int64_t>(hot_chunks, 1) * 64;
                             GRB_DISPATCH_TYPE(A->type->code, T, {
-                                hipLaunchKernelGGL((k_hrec_init<T>), dim3((unsigned)ceil_div(n_rec, 256)), dim3(256), 0, ctx().stream, A->d_hrec, n_rec,
-                                                   A->hrec_bytes, hot_pad_code<T>(LONG_LDS_WORDS));
+                                hipLaunchKernelGGL((k_hrec_init<T>), dim3((unsigned)ceil_div(n_rec, 256)), dim3(256), 0, ctx().stream, sp.strips.d_hrec, n_rec,
+                                                   sp.strips.hrec_bytes, hot_pad_code<T>(LONG_LDS_WORDS));
                             })
                         }
                     }
@@ -504,10 +478,10 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                         hipLaunchKernelGGL((k_strip_place<T>), dim3((unsigned)nblk), dim3(STRIP_CH), 0, ctx().stream, (const uint64_t *)keys2.p,
                                            (const uint32_t *)idx2.p, n_strip, (const int64_t *)blk.p, (const int64_t *)seg_first.p,
                                            (const int64_t *)off.p, (const int64_t *)cshift.p, nl, strip_sub, col_src, (const T *)A->d_val,
-                                           A->iso ? 1 : 0, A->cls_lds_lim, ncls, A->d_lcol, (T *)A->d_lval, A->d_sstart, A->d_sslot,
-                                           A->d_hrec, A->hrec_bytes, hot_chunks * STRIP_CH, hot_cls,
-                                           use_dict ? (const unsigned long long *)A->d_vd_table : (const unsigned long long *)nullptr,
-                                           use_dict ? (const unsigned char *)A->d_vd_codes : (const unsigned char *)nullptr, hub_ncls, (int)hub_lim);
+                                           A->iso ? 1 : 0, sp.cls_lds_lim, ncls, sp.d_lcol, (T *)sp.d_lval.get(), sp.strips.d_sstart, sp.strips.d_sslot,
+                                           sp.strips.d_hrec, sp.strips.hrec_bytes, hot_chunks * STRIP_CH, hot_cls,
+                                           use_dict ? (const unsigned long long *)A->vd.d_vd_table : (const unsigned long long *)nullptr,
+                                           use_dict ? (const unsigned char *)A->vd.d_vd_codes : (const unsigned char *)nullptr, hub_ncls, (int)hub_lim);
                     })
                     {
                         int64_t h_end[MAXC];
@@ -515,32 +489,24 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                         DevBuf<int64_t> cend(MAXC);
                         h2d(cend.p, h_end, sizeof(int64_t) * (size_t)nvc);
                         hipLaunchKernelGGL(k_strip_pad_starts, dim3(1), dim3(128), 0, ctx().stream, (const int64_t *)sc.p, (const int64_t *)off.p,
-                                           (const int64_t *)cshift.p, (const int64_t *)cend.p, nvc, A->d_sstart);
+                                           (const int64_t *)cshift.p, (const int64_t *)cend.p, nvc, sp.strips.d_sstart);
                         sync_stream();
                     }
                     // round 6: the slots as 16-bit offsets from each chunk's smallest slot (half the slot stream of the strip kernels)
-                    dev_free(A->d_sslot16); dev_free(A->d_sslot_base);
-                    A->d_sslot16 = nullptr; A->d_sslot_base = nullptr;
                     if (ctx().strip_slot16 && nch > 0) {
                         DevBuf<unsigned int> too_wide(1, true);
-                        uint16_t *s16 = (uint16_t *)dev_alloc(sizeof(uint16_t) * (size_t)(padded / 8));
-                        int32_t *sb = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nch);
-                        hipLaunchKernelGGL(k_strip_slot16, dim3((unsigned)ceil_div(nch, 4)), dim3(256), 0, ctx().stream, (const int32_t *)A->d_sslot, nch, s16, sb, too_wide.p);
+                        DevPtr<uint16_t> s16((uint16_t *)dev_alloc(sizeof(uint16_t) * (size_t)(padded / 8)));
+                        DevPtr<int32_t> sb((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nch));
+                        hipLaunchKernelGGL(k_strip_slot16, dim3((unsigned)ceil_div(nch, 4)), dim3(256), 0, ctx().stream, (const int32_t *)sp.strips.d_sslot, nch, s16.get(), sb.get(), too_wide.p);
                         unsigned int wide = 0;
                         d2h(&wide, too_wide.p, sizeof(wide));
-                        if (wide) {  // (a chunk whose rows lie 65535 slots apart: the 32-bit slots stay)
-                            dev_free(s16);
-                            dev_free(sb);
-                        } else {
-                            A->d_sslot16 = s16;
-                            A->d_sslot_base = sb;
-                            dev_free(A->d_sslot);
-                            A->d_sslot = nullptr;
+                        if (!wide) {  // (else a chunk whose rows lie 65535 slots apart: the 32-bit slots stay)
+                            sp.strips.d_sslot16 = std::move(s16);
+                            sp.strips.d_sslot_base = std::move(sb);
+                            sp.strips.d_sslot.reset();
                         }
                     }
-                    for (int c = 0; c <= nvc; c++) A->strip_cb[c] = h_cb[c];
-                    dev_free(A->d_wg_tab); dev_free(A->d_strip_cb);
-                    A->d_wg_tab = nullptr; A->d_strip_cb = nullptr; A->wg_tab_g = 0;
+                    for (int c = 0; c <= nvc; c++) sp.strips.strip_cb[c] = h_cb[c];
                     if (hub_ncls > 0) {
                         // one launch of the fast strip kernel over both levels: the persistent workgroups (one per CU) are dealt to the nvc
                         // classes by chunk count -- every class with chunks gets one, the rest go to whichever class has the most chunks
@@ -585,20 +551,20 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                             int32_t *t = &tab[(size_t)b * 5];
                             t[0] = 0; t[1] = 0; t[2] = ncls; t[3] = 1 << 28; t[4] = 1;
                         }
-                        A->d_wg_tab = (int32_t *)dev_alloc(sizeof(int32_t) * tab.size());
-                        h2d(A->d_wg_tab, tab.data(), sizeof(int32_t) * tab.size());
-                        A->d_strip_cb = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(nvc + 1));
-                        h2d(A->d_strip_cb, h_cb, sizeof(int64_t) * (size_t)(nvc + 1));
-                        A->wg_tab_g = G;
+                        sp.strips.d_wg_tab.reset((int32_t *)dev_alloc(sizeof(int32_t) * tab.size()));
+                        h2d(sp.strips.d_wg_tab, tab.data(), sizeof(int32_t) * tab.size());
+                        sp.strips.d_strip_cb.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(nvc + 1)));
+                        h2d(sp.strips.d_strip_cb, h_cb, sizeof(int64_t) * (size_t)(nvc + 1));
+                        sp.strips.wg_tab_g = G;
                     }
                     if (getenv("GRB_PRINT_STRIPS")) {  // (diagnostic: chunks per class -- a persistent class with more chunks than the others sets the kernel's time)
                         fprintf(stderr, "[strips kind %d] %d classes (%d of them the hub level's), chunks per class:", kind, nvc, hub_ncls);
                         for (int c = 0; c < nvc; c++) fprintf(stderr, " %lld", (long long)(h_cb[c + 1] - h_cb[c]));
                         fprintf(stderr, "  segments %lld\n", (long long)nseg);
                     }
-                    A->strip_ncls = ncls;
-                    A->strip_nseg = nseg;
-                    A->long_nnz = nnz_long;
+                    sp.strips.strip_ncls = ncls;
+                    sp.strips.strip_nseg = nseg;
+                    sp.long_nnz = nnz_long;
                     sync_stream();  // (the temporaries above are released at the end of this scope)
                 }
             }
@@ -606,7 +572,6 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
             //  kernel that streams them all -- and the cold tiles 7 % SLOWER: their stream is a third of their time, the code load + LDS
             //  lookup per entry costs more than the bytes it saves.  The tiles keep full values.)
             const bool use_dict_all = ct_mode == 2;  // (round 6: behind the packed words the codes were measured again -- profiles/r06/ctile_pack.txt)
-            A->ct_mode = 0;
             if (kind == 4 && nnz_long > n_strip) {
                 // the cold entries as tagged tiles: a (column range, slot block) pair is one tile, or several when it holds more than
                 // CT_MAX_ENTRIES entries (the hub rows: the sorted run is cut into equal pieces -- a piece still lies inside the
@@ -657,32 +622,31 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 std::vector<int32_t> h_order;
                 h_order.reserve((size_t)nt);
                 for (int x = 0; x < 8; x++) {
-                    A->ct_xoff[x] = (int64_t)h_order.size();
+                    sp.cold.ct_xoff[x] = (int64_t)h_order.size();
                     for (int64_t t = 0; t < nt; t++)
                         if (range_xcd[(size_t)tile_range[(size_t)t]] == x) h_order.push_back((int32_t)t);
                 }
-                A->ct_xoff[8] = (int64_t)h_order.size();
+                sp.cold.ct_xoff[8] = (int64_t)h_order.size();
                 const size_t ents = (size_t)std::max<int64_t>(units, 1) * CT_EPL;
                 // (packed: behind the nt tile records, the first column code of every tile's range -- int32[nt])
-                A->d_ct_tiles = dev_alloc((sizeof(CTile) + sizeof(int32_t)) * (size_t)std::max<int64_t>(nt, 1));
-                h2d(A->d_ct_tiles, h_tiles.data(), sizeof(CTile) * (size_t)nt);
+                sp.cold.d_ct_tiles.reset(dev_alloc((sizeof(CTile) + sizeof(int32_t)) * (size_t)std::max<int64_t>(nt, 1)));
+                h2d(sp.cold.d_ct_tiles, h_tiles.data(), sizeof(CTile) * (size_t)nt);
                 if (ct_mode) {
                     std::vector<int32_t> h_cbase((size_t)nt);
                     for (int64_t t = 0; t < nt; t++) h_cbase[(size_t)t] = h_bounds[(size_t)tile_range[(size_t)t]];
-                    h2d((char *)A->d_ct_tiles + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1), h_cbase.data(), sizeof(int32_t) * (size_t)nt);
+                    h2d((char *)sp.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1), h_cbase.data(), sizeof(int32_t) * (size_t)nt);
                 }
-                dev_free(A->d_ct_order);
-                A->d_ct_order = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nt, 1));
-                h2d(A->d_ct_order, h_order.data(), sizeof(int32_t) * (size_t)nt);
+                sp.cold.d_ct_order.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nt, 1)));
+                h2d(sp.cold.d_ct_order, h_order.data(), sizeof(int32_t) * (size_t)nt);
                 DevBuf<int64_t> efirst(nt + 1);
                 h2d(efirst.p, h_efirst.data(), sizeof(int64_t) * (size_t)(nt + 1));
-                A->d_ct_col = (int32_t *)dev_alloc(sizeof(int32_t) * ents);
+                sp.cold.d_ct_col.reset((int32_t *)dev_alloc(sizeof(int32_t) * ents));
                 const size_t ct_vb = use_dict_all ? 1 : A->type->size;  // (dictionary-coded matrices: one byte per value)
-                A->d_ct_val = A->iso ? nullptr : dev_alloc(ct_vb * ents);
-                A->d_ct_loc = ct_mode ? nullptr : (uint16_t *)dev_alloc(sizeof(uint16_t) * ents);
-                GRB_HIP(hipMemsetAsync(A->d_ct_col, 0xff, sizeof(int32_t) * ents, ctx().stream));  // (padding: column -1 / the packed word 0xffffffff)
-                if (A->d_ct_val) GRB_HIP(hipMemsetAsync(A->d_ct_val, 0, ct_vb * ents, ctx().stream));
-                if (A->d_ct_loc) GRB_HIP(hipMemsetAsync(A->d_ct_loc, 0, sizeof(uint16_t) * ents, ctx().stream));
+                sp.cold.d_ct_val.reset(A->iso ? nullptr : dev_alloc(ct_vb * ents));
+                sp.cold.d_ct_loc.reset(ct_mode ? nullptr : (uint16_t *)dev_alloc(sizeof(uint16_t) * ents));
+                GRB_HIP(hipMemsetAsync(sp.cold.d_ct_col, 0xff, sizeof(int32_t) * ents, ctx().stream));  // (padding: column -1 / the packed word 0xffffffff)
+                if (sp.cold.d_ct_val) GRB_HIP(hipMemsetAsync(sp.cold.d_ct_val, 0, ct_vb * ents, ctx().stream));
+                if (sp.cold.d_ct_loc) GRB_HIP(hipMemsetAsync(sp.cold.d_ct_loc, 0, sizeof(uint16_t) * ents, ctx().stream));
                 const int64_t n_cold = nnz_long - n_strip;
                 {
                     // inside a tile the entries go by column code: neighbouring lanes gather from the same lines (grb_mxv_ctile.inc)
@@ -696,18 +660,16 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                     GRB_DISPATCH_TYPE(A->type->code, T, {
                         hipLaunchKernelGGL((k_ctile_place<T>), dim3((unsigned)ceil_div(n_cold, 256)), dim3(256), 0, ctx().stream, (const uint64_t *)keys2.p,
                                            (const uint32_t *)idx2.p, n_strip, n_cold, (const uint64_t *)key2s.p, (const uint32_t *)pays.p, (const int64_t *)efirst.p,
-                                           (const CTile *)A->d_ct_tiles, (const T *)A->d_val, A->iso ? 1 : 0, A->d_ct_col, (T *)A->d_ct_val, A->d_ct_loc,
-                                           use_dict_all ? (const unsigned long long *)A->d_vd_table : (const unsigned long long *)nullptr,
-                                           use_dict_all ? (const unsigned char *)A->d_vd_codes : (const unsigned char *)nullptr,
-                                           ct_mode ? (const int32_t *)((const char *)A->d_ct_tiles + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1)) : (const int32_t *)nullptr);
+                                           (const CTile *)sp.cold.d_ct_tiles.get(), (const T *)A->d_val, A->iso ? 1 : 0, sp.cold.d_ct_col, (T *)sp.cold.d_ct_val.get(), sp.cold.d_ct_loc,
+                                           use_dict_all ? (const unsigned long long *)A->vd.d_vd_table : (const unsigned long long *)nullptr,
+                                           use_dict_all ? (const unsigned char *)A->vd.d_vd_codes : (const unsigned char *)nullptr,
+                                           ct_mode ? (const int32_t *)((const char *)sp.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1)) : (const int32_t *)nullptr);
                     })
                     sync_stream();
                 }
-                A->ct_mode = ct_mode;
-                A->ct_nsb = n_sb;
-                A->ct_ncr = n_cr;
-                A->ct_ntiles = nt;
-                A->ct_units = units;
+                sp.cold.ct_mode = ct_mode;
+                sp.cold.ct_ntiles = nt;
+                sp.cold.ct_units = units;
                 if (getenv("GRB_PRINT_STRIPS")) {
                     fprintf(stderr, "[cold tiles] mode %d (slots %d), %d column ranges, %lld tiles, entries per range:", ct_mode, ct_slots, n_cr, (long long)nt);
                     for (int r = 0; r < n_cr; r++) fprintf(stderr, " %lld(x%d)", (long long)range_cnt[(size_t)r], range_xcd[(size_t)r]);
@@ -732,51 +694,49 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 hipLaunchKernelGGL(k_long_item_fill, dim3((unsigned)ceil_div(nv, 256)), dim3(256), 0, ctx().stream,
                                    (const int64_t *)vptr.p, nv, nl, (const int64_t *)icnt.p, ikey.p, iid.p, isrc.p, ilen.p, islot.p);
                 prim_sort_pairs_u64_u32(ikey.p, ikey2.p, iid.p, iorder.p, ni, 19);  // 11 bits of length under the virtual class (< 128)
-                A->d_it_len = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)ni);
-                A->d_it_slot = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)ni);
-                A->d_it_start = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(ni + 1));
+                sp.d_it_len.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)ni));
+                sp.d_it_slot.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)ni));
+                sp.d_it_start.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(ni + 1)));
                 hipLaunchKernelGGL(k_long_item_order, dim3((unsigned)ceil_div(ni + 1, 256)), dim3(256), 0, ctx().stream,
                                    (const uint32_t *)iorder.p, ni, (const int64_t *)isrc.p, (const int32_t *)ilen.p,
-                                   (const int32_t *)islot.p, osrc.p, A->d_it_len, A->d_it_slot, len4.p);
-                prim_exclusive_sum_i64(len4.p, A->d_it_start, ni + 1);
+                                   (const int32_t *)islot.p, osrc.p, sp.d_it_len, sp.d_it_slot, len4.p);
+                prim_exclusive_sum_i64(len4.p, sp.d_it_start, ni + 1);
                 int64_t padded = 0;
-                d2h(&padded, A->d_it_start + ni, 8);
-                A->d_item_begin = (int64_t *)dev_alloc(sizeof(int64_t) * 9);
-                hipLaunchKernelGGL(k_long_class_bounds, dim3(1), dim3(64), 0, ctx().stream, (const uint64_t *)ikey2.p, ni, A->d_item_begin, sub);
-                d2h(A->item_begin, A->d_item_begin, sizeof(int64_t) * 9);
+                d2h(&padded, sp.d_it_start + ni, 8);
+                sp.d_item_begin.reset((int64_t *)dev_alloc(sizeof(int64_t) * 9));
+                hipLaunchKernelGGL(k_long_class_bounds, dim3(1), dim3(64), 0, ctx().stream, (const uint64_t *)ikey2.p, ni, sp.d_item_begin, sub);
+                d2h(sp.item_begin, sp.d_item_begin, sizeof(int64_t) * 9);
                 // (+2048 entries: a group's steps run to the longest item of its quad, i.e. past its own entries)
                 // only codes of the hot table are classed by line (k_long_keys): those may live in LDS
-                A->cls_lds_lim = (int)std::min<int64_t>(hot ? A->hot_k : 0,
+                sp.cls_lds_lim = (int)std::min<int64_t>(hot ? A->hot.hot_k : 0,
                                                         long_lds_codes((int)A->type->size, A->type->code == TC_BOOL, LONG_LDS_WORDS));
-                A->d_lcol = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(padded + 2048));
-                A->d_lval = A->iso ? nullptr : dev_alloc(A->type->size * (size_t)(padded + 2048));
+                sp.d_lcol.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(padded + 2048)));
+                sp.d_lval.reset(A->iso ? nullptr : dev_alloc(A->type->size * (size_t)(padded + 2048)));
                 GRB_DISPATCH_TYPE(A->type->code, T, {
-                    hipLaunchKernelGGL((k_long_place<T>), dim3((unsigned)ni), dim3(64), 0, ctx().stream, (const int64_t *)A->d_it_start,
-                                       (const int64_t *)osrc.p, (const int32_t *)A->d_it_len, (const uint32_t *)idx2.p, col_src,
-                                       (const T *)A->d_val, A->iso ? 1 : 0, A->d_lcol, (T *)A->d_lval, A->cls_lds_lim);
+                    hipLaunchKernelGGL((k_long_place<T>), dim3((unsigned)ni), dim3(64), 0, ctx().stream, (const int64_t *)sp.d_it_start,
+                                       (const int64_t *)osrc.p, (const int32_t *)sp.d_it_len, (const uint32_t *)idx2.p, col_src,
+                                       (const T *)A->d_val, A->iso ? 1 : 0, sp.d_lcol, (T *)sp.d_lval.get(), sp.cls_lds_lim);
                 })
-                GRB_HIP(hipMemsetAsync(A->d_lcol + padded, 0xff, sizeof(int32_t) * 2048, ctx().stream));
-                if (A->d_lval) GRB_HIP(hipMemsetAsync((char *)A->d_lval + A->type->size * (size_t)padded, 0, A->type->size * 2048, ctx().stream));
-                A->n_items = ni;
-                A->long_nnz = nnz_long;
+                GRB_HIP(hipMemsetAsync(sp.d_lcol + padded, 0xff, sizeof(int32_t) * 2048, ctx().stream));
+                if (sp.d_lval) GRB_HIP(hipMemsetAsync((char *)sp.d_lval.get() + A->type->size * (size_t)padded, 0, A->type->size * 2048, ctx().stream));
+                sp.n_items = ni;
+                sp.long_nnz = nnz_long;
                 sync_stream();  // (the temporaries above are released at the end of this scope)
             }
             }
         }
         sync_stream();
-    } catch (...) {
-        matrix_free(S);
-        throw;
     }
-    A->short_part = S;
-    A->d_long_bits = lbits.release();
-    A->n_long = nl;
-    A->n_chunks = nc;
-    A->split_hot = hot;
-    A->split_kind = kind;
-    A->split_state = 1;
-    A->tails_max_len = tail_max;
-    A->short_tagged_only = false;
+    sp.d_long_bits.reset(lbits.release());
+    sp.n_long = nl;
+    sp.n_chunks = nc;
+    sp.split_hot = hot;
+    sp.split_kind = kind;
+    sp.split_state = 1;
+    sp.tails_max_len = tail_max;
+    A->split = std::move(sp);
+    // (the layouts of the short rows are built from the split that is now A's -- each commits itself; should one of them throw, A keeps a
+    //  complete split whose short part still has its CSR arrays)
     if (want_tagged_only && S->nrows == A->nrows && S->nvals < 0x1ffffffffll) {
         // the tagged row groups are the only form of the short rows' entries the kernels read: the CSR copy they were built from is
         // released (0.42 GB of the cached layouts at scale 24); the row pointers stay (row lengths, accounting)
@@ -788,22 +748,25 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
         //  Kronecker-26 block 0.636 -> 0.652 (profiles/r05/final_run_summary_tiles_on_natural_layouts.txt) -- behind a 2 MiB hot table the
         //  codes of the other columns are original labels: sorting by them gathers nothing together)
         if (ctx().rows_tile && (A->hot_identity || (hot && ctx().rows_tile == 2))) ensure_rtile(A);
-        if (A->rt_state != 1 || !ctx().lazy_tagged) ensure_tagged(A);
+        if (A->split.rtile.rt_state != 1 || !ctx().lazy_tagged) ensure_tagged(A);
         dev_free(S->d_col);
         S->d_col = nullptr;
         if (!S->iso) {
             dev_free(S->d_val);
             S->d_val = nullptr;
         }
-        A->short_tagged_only = true;
+        A->split.short_tagged_only = true;
     }
     // the short part and the strips / items carry their own re-coded columns: the re-coded copy of the whole array is only read
     // again by a product that cannot take the split (a typecast of the values), which falls back to the plain arrays
-    if (hot && ctx().drop_hot_cols && nc > 0 && A->long_nnz > 0 && (kind == 1 || kind == 2 || kind == 4) && A->d_col_hot) {
-        dev_free(A->d_col_hot);
-        A->d_col_hot = nullptr;
-        if (A->hot_identity) A->d_col = nullptr;  // (the same array)
-        A->hot_cols_dropped = true;
+    if (hot && ctx().drop_hot_cols && nc > 0 && A->split.long_nnz > 0 && (kind == 1 || kind == 2 || kind == 4) && A->col_hot()) {
+        if (A->hot_identity) {  // (an ordered twin: the codes are its own column array)
+            dev_free(A->d_col);
+            A->d_col = nullptr;
+        } else {
+            A->hot.d_col_hot.reset();
+        }
+        A->hot.hot_cols_dropped = true;
     }
 }
 
@@ -828,20 +791,20 @@ static GB_Perm *ensure_perm(GB_Matrix_opaque *S, int64_t k_hot, DevBuf<unsigned 
 {
     const int64_t n = (int64_t)S->ncols, nnz = S->nvals;
     GB_Matrix_opaque *partner = S->tr ? S->tr : S->tr_of;
-    const bool adopt = !S->perm && partner && partner->perm;
+    const bool adopt = !S->order.perm && partner && partner->order.perm;
     if (adopt) {
-        S->perm = partner->perm;
-        perm_retain(S->perm);
+        S->order.perm = partner->order.perm;
+        perm_retain(S->order.perm);
     }
     // (the reference counts by position steer the column ranges of the cold tiles: needed with an adopted order as well)
     DevBuf<unsigned int> cnt(n, true);
     const int hstride = nnz >= ((int64_t)1 << 26) ? 8 : 1;
     hipLaunchKernelGGL(k_hot_hist, dim3((unsigned)ceil_div(nnz, 256 * hstride)), dim3(256), 0, ctx().stream, S->d_col, nnz, cnt.p, hstride);
-    if (S->perm) {
+    if (S->order.perm) {
         hipLaunchKernelGGL(k_order_poscnt, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx().stream, (const unsigned int *)cnt.p,
-                           (const int32_t *)S->perm->d_inv, n, poscnt.p);
+                           (const int32_t *)S->order.perm->d_inv, n, poscnt.p);
         sync_stream();
-        return S->perm;
+        return S->order.perm;
     }
     DevBuf<uint64_t> keys(n), keys2(n);
     DevBuf<uint32_t> ids(n), ids2(n);
@@ -863,26 +826,26 @@ static GB_Perm *ensure_perm(GB_Matrix_opaque *S, int64_t k_hot, DevBuf<unsigned 
         perm_release(P);
         throw;
     }
-    S->perm = P;
-    if (partner && !partner->perm) {
-        partner->perm = P;
+    S->order.perm = P;
+    if (partner && !partner->order.perm) {
+        partner->order.perm = P;
         perm_retain(P);
     }
     return P;
 }
 
-// ord = P S P' with its pull layouts; S->ord_state = 1, or -1 when the matrix does not take them (no skew: the split declines)
+// ord = P S P' with its pull layouts; S->order.ord_state = 1, or -1 when the matrix does not take them (no skew: the split declines)
 static void ensure_ordered(GB_Matrix_opaque *S)
 {
     const uint64_t sig = order_signature();
-    if (S->ord_state == 1 && S->ord && S->ord_sig == sig) return;
-    if (S->ord_state == -1 && S->ord_sig == sig) return;
-    if (S->ord) {  // (built under other layout options)
-        matrix_free(S->ord);
-        S->ord = nullptr;
+    if (S->order.ord_state == 1 && S->order.ord && S->order.ord_sig == sig) return;
+    if (S->order.ord_state == -1 && S->order.ord_sig == sig) return;
+    if (S->order.ord) {  // (built under other layout options)
+        matrix_free(S->order.ord);
+        S->order.ord = nullptr;
     }
-    S->ord_state = -1;
-    S->ord_sig = sig;
+    S->order.ord_state = -1;
+    S->order.ord_sig = sig;
     const int64_t n = (int64_t)S->ncols, nnz = S->nvals;
     if (n + (int64_t)(1 << 22) > 0x7fffffff || nnz >= 0xf0000000ll) return;
     const size_t vb = S->type->size;
@@ -896,10 +859,10 @@ static void ensure_ordered(GB_Matrix_opaque *S)
     const int64_t m_rows = (int64_t)S->nrows;
     // A row block set up for a sharded run (GrX_Matrix_shard_setup, round 6): the column order came from the GLOBAL reference counts -- the
     // same on every rank --, the rows stay as they are: the twin is the block with its columns renamed, any shape.
-    if (S->col_order_only && !S->perm) S->col_order_only = false;
-    const bool col_only = !ranked && S->col_order_only;
+    if (S->order.col_order_only && !S->order.perm) S->order.col_order_only = false;
+    const bool col_only = !ranked && S->order.col_order_only;
     if (!ranked && !col_only && S->nrows != S->ncols) return;  // (an order of the library's own needs one vertex space)
-    GB_Perm *P = ranked ? nullptr : (col_only ? S->perm : ensure_perm(S, k_hot, poscnt));
+    GB_Perm *P = ranked ? nullptr : (col_only ? S->order.perm : ensure_perm(S, k_hot, poscnt));
     GB_Matrix_opaque *R = matrix_new(S->type, S->nrows, S->ncols);
     try {
       if (col_only) {
@@ -961,13 +924,12 @@ static void ensure_ordered(GB_Matrix_opaque *S)
             hipLaunchKernelGGL(k_twin_live_rows, dim3((unsigned)ceil_div(m_rows, 1024)), dim3(1024), 0, ctx().stream, (const int64_t *)R->d_ptr, m_rows, last.p);
             unsigned long long h_last = 0;
             d2h(&h_last, last.p, sizeof(h_last));
-            R->ord_live_rows = (int64_t)h_last;
+            R->order.ord_live_rows = (int64_t)h_last;
         }
         // ---- its column codes ARE the hot codes: positions below k_hot are the table, the operand is the image
-        R->hot_state = 1;
-        R->hot_k = k_hot;
+        R->hot.hot_state = 1;
+        R->hot.hot_k = k_hot;
         R->hot_identity = true;
-        R->d_col_hot = R->d_col;
         // ---- column ranges of the cold tiles: behind the LDS-resident codes, about equal reference counts, at most ~2 MiB of operand
         {
             const int ncls = (ctx().long_classes == 16 || ctx().long_classes == 32 || ctx().long_classes == 64) ? ctx().long_classes : 8;
@@ -1002,16 +964,16 @@ static void ensure_ordered(GB_Matrix_opaque *S)
                 }
             }
             bounds.push_back((int32_t)n);
-            R->ct_ncr = (int)bounds.size() - 1;
-            R->d_cold_bounds = (int32_t *)dev_alloc(sizeof(int32_t) * bounds.size());
-            h2d(R->d_cold_bounds, bounds.data(), sizeof(int32_t) * bounds.size());
+            R->order.ct_ncr = (int)bounds.size() - 1;
+            R->order.d_cold_bounds.reset((int32_t *)dev_alloc(sizeof(int32_t) * bounds.size()));
+            h2d(R->order.d_cold_bounds, bounds.data(), sizeof(int32_t) * bounds.size());
         }
         sync_stream();
         // ---- the layouts (hot strips, cold tiles, tagged row groups) in that order
-        ensure_split(R, R->d_col_hot, true);
+        ensure_split(R, R->col_hot(), true);
         // (hot strips + cold tiles, or -- BOOL matrices -- class items; the short rows as tagged row groups either way)
-        const bool usable = R->split_state == 1 && R->long_nnz > 0 && R->short_tagged_only &&
-                            ((R->split_kind == 4 && (R->strip_nseg > 0 || R->ct_units > 0)) || (R->split_kind == 1 && R->n_items > 0));
+        const bool usable = R->split.split_state == 1 && R->split.long_nnz > 0 && R->split.short_tagged_only &&
+                            ((R->split.split_kind == 4 && (R->split.strips.strip_nseg > 0 || R->split.cold.ct_units > 0)) || (R->split.split_kind == 1 && R->split.n_items > 0));
         if (!usable) {
             matrix_free(R);
             return;
@@ -1020,8 +982,7 @@ static void ensure_ordered(GB_Matrix_opaque *S)
         if (R->d_col) {
             dev_free(R->d_col);
             R->d_col = nullptr;
-            R->d_col_hot = nullptr;
-            R->hot_cols_dropped = true;
+            R->hot.hot_cols_dropped = true;
         }
         if (!R->iso) {
             dev_free(R->d_val);
@@ -1031,77 +992,85 @@ static void ensure_ordered(GB_Matrix_opaque *S)
         matrix_free(R);
         throw;
     }
-    S->ord = R;
-    S->ord_state = 1;
+    S->order.ord = R;
+    S->order.ord_state = 1;
 }
 
 // tagged row groups of the short part S of A (once per matrix; see grb_mxv_rows_tag.inc)
 // offsets of the row groups (units of TAG_EPL entries) and their "row has an entry" words: from the short part's row pointers alone
 static void ensure_tagged_index(GB_Matrix_opaque *A)
 {
-    if (A->tg_state != 0) return;
-    GB_Matrix_opaque *S = A->short_part;
+    if (A->split.tagged.tg_state != 0) return;
+    GB_Matrix_opaque *S = A->split.short_part.get();
     const int64_t m = (int64_t)S->nrows, ngroups = ceil_div(m, 64);
     const int64_t *sptr = matrix_rowptr(S);
     DevBuf<int64_t> cnt(ngroups + 1);
-    A->d_tg_nonempty = (uint64_t *)dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(ngroups, 1));
+    GB_Matrix_opaque::TaggedGroups tg;
+    tg.d_tg_nonempty.reset((uint64_t *)dev_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(ngroups, 1)));
     hipLaunchKernelGGL(k_tag_count, dim3((unsigned)ceil_div((ngroups + 1) * 64, 256)), dim3(256), 0, ctx().stream, sptr, m, ngroups, cnt.p,
-                       A->d_tg_nonempty);
+                       tg.d_tg_nonempty.get());
     prim_exclusive_sum_i64(cnt.p, cnt.p, ngroups + 1);
     int64_t units = 0;
     d2h(&units, cnt.p + ngroups, 8);
     if (units >= 0x7ffffff0ll) fail(GrB_NOT_IMPLEMENTED, "tagged row groups: too many entries for 32-bit group offsets");  // (unreachable below 2^33 entries: ensure_split's guard)
-    A->d_tg_off = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(ngroups + 1));
+    tg.d_tg_off.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(ngroups + 1)));
     hipLaunchKernelGGL(k_tag_off32, dim3((unsigned)ceil_div(ngroups + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)cnt.p, ngroups + 1,
-                       A->d_tg_off);
+                       tg.d_tg_off.get());
     sync_stream();  // (cnt is released at the end of this scope)
-    A->tg_units = units;
-    A->tg_state = 2;
+    tg.tg_units = units;
+    tg.tg_state = 2;
+    A->split.tagged = std::move(tg);
 }
 // ... and their entries: from the short part's CSR arrays (layout build), or -- those are gone and the short rows have sorted row tiles: round 6,
 // Context::lazy_tagged -- from the tiles, at the first call the tiles do not take
 static void ensure_tagged(GB_Matrix_opaque *A)
 {
-    if (A->tg_state == 1) return;
+    if (A->split.tagged.tg_state == 1) return;
     ensure_tagged_index(A);
-    GB_Matrix_opaque *S = A->short_part;
+    GB_Matrix_opaque *S = A->split.short_part.get();
+    GB_Matrix_opaque::TaggedGroups &tg = A->split.tagged;
+    const GB_Matrix_opaque::RowTiles &rt = A->split.rtile;
     const bool from_csr = S->d_col != nullptr || S->nvals == 0;
-    if (!from_csr && A->rt_state != 1) fail(GrB_PANIC, "tagged row groups: the short part's CSR arrays were released and it has no row tiles (internal error)");
+    if (!from_csr && rt.rt_state != 1) fail(GrB_PANIC, "tagged row groups: the short part's CSR arrays were released and it has no row tiles (internal error)");
     const int64_t m = (int64_t)S->nrows, ngroups = ceil_div(m, 64);
     const int64_t *sptr = matrix_rowptr(S);
-    const int64_t units = A->tg_units;
+    const int64_t units = tg.tg_units;
     const size_t ents = (size_t)std::max<int64_t>(units, 1) * TAG_EPL;
-    A->d_tg_col = (int32_t *)dev_alloc(sizeof(int32_t) * ents);
-    const bool dict = A->vdict_n > 0;  // (dictionary-coded matrices: one byte per value)
+    // (the entries are built into owners of their own and join the group with its state: a throw on the way leaves the index as it was)
+    DevPtr<int32_t> tg_col((int32_t *)dev_alloc(sizeof(int32_t) * ents));
+    const bool dict = A->vd.vdict_n > 0;  // (dictionary-coded matrices: one byte per value)
     const size_t tg_vb = dict ? 1 : S->type->size;
-    A->d_tg_val = S->iso ? nullptr : dev_alloc(tg_vb * ents);
-    A->d_tg_tag = (unsigned char *)dev_alloc(ents);
-    GRB_HIP(hipMemsetAsync(A->d_tg_col, 0xff, sizeof(int32_t) * ents, ctx().stream));
-    if (A->d_tg_val) GRB_HIP(hipMemsetAsync(A->d_tg_val, 0, tg_vb * ents, ctx().stream));
-    GRB_HIP(hipMemsetAsync(A->d_tg_tag, 0x40, ents, ctx().stream));
+    DevPtr<void> tg_val(S->iso ? nullptr : dev_alloc(tg_vb * ents));
+    DevPtr<unsigned char> tg_tag((unsigned char *)dev_alloc(ents));
+    GRB_HIP(hipMemsetAsync(tg_col, 0xff, sizeof(int32_t) * ents, ctx().stream));
+    if (tg_val) GRB_HIP(hipMemsetAsync(tg_val, 0, tg_vb * ents, ctx().stream));
+    GRB_HIP(hipMemsetAsync(tg_tag, 0x40, ents, ctx().stream));
     if (from_csr) {
         GRB_DISPATCH_TYPE(S->type->code, T, {
             hipLaunchKernelGGL((k_tag_fill<T>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream, sptr, (const int32_t *)S->d_col,
-                               (const T *)S->d_val, S->iso ? 1 : 0, m, (const int32_t *)A->d_tg_off, A->d_tg_col, (T *)A->d_tg_val, A->d_tg_tag,
-                               dict ? (const unsigned long long *)A->d_vd_table : (const unsigned long long *)nullptr,
-                               dict ? (const unsigned char *)A->d_vd_codes : (const unsigned char *)nullptr);
+                               (const T *)S->d_val, S->iso ? 1 : 0, m, (const int32_t *)tg.d_tg_off, tg_col.get(), (T *)tg_val.get(), tg_tag.get(),
+                               dict ? (const unsigned long long *)A->vd.d_vd_table : (const unsigned long long *)nullptr,
+                               dict ? (const unsigned char *)A->vd.d_vd_codes : (const unsigned char *)nullptr);
         })
     } else {
         // (the tiles hold every entry of the short part: column code, row inside the tile, value or value code)
         const bool is_bool = S->type->code == TC_BOOL;
-        const int rows4 = A->rt_rows4 == 16384 ? 16384 : 8192;
+        const int rows4 = rt.rt_rows4 == 16384 ? 16384 : 8192;
         const int rows_cap = (S->type->size > 4 && !is_bool) ? rows4 / 2 : rows4;
-        const int vmode = S->iso ? 0 : (dict ? (A->d_rt_val ? 1 : -1) : (int)S->type->size);
+        const int vmode = S->iso ? 0 : (dict ? (rt.d_rt_val ? 1 : -1) : (int)S->type->size);
         DevBuf<int32_t> gcnt(ngroups + 1, true);
         GRB_DISPATCH_TYPE(S->type->code, T, {
-            hipLaunchKernelGGL((k_tag_from_tiles<T>), dim3((unsigned)A->rt_ntiles), dim3(1024), 0, ctx().stream, (const RTile *)A->d_rt_tiles, (const int32_t *)A->d_rt_col,
-                               (const uint16_t *)A->d_rt_tag, (const void *)A->d_rt_val, vmode, rows_cap, (const int32_t *)A->d_tg_off, gcnt.p, A->d_tg_col, A->d_tg_val,
-                               A->d_tg_tag);
+            hipLaunchKernelGGL((k_tag_from_tiles<T>), dim3((unsigned)rt.rt_ntiles), dim3(1024), 0, ctx().stream, (const RTile *)rt.d_rt_tiles.get(), (const int32_t *)rt.d_rt_col,
+                               (const uint16_t *)rt.d_rt_tag, (const void *)rt.d_rt_val.get(), vmode, rows_cap, (const int32_t *)tg.d_tg_off, gcnt.p, tg_col.get(), tg_val.get(),
+                               tg_tag.get());
         })
         sync_stream();  // (gcnt is released at the end of this scope)
     }
     sync_stream();
-    A->tg_state = 1;
+    tg.d_tg_col = std::move(tg_col);
+    tg.d_tg_val = std::move(tg_val);
+    tg.d_tg_tag = std::move(tg_tag);
+    tg.tg_state = 1;
 }
 
 // sorted row tiles of the short part S of an ordered twin A (once per matrix; see grb_mxv_rtile.inc).  Needs the tagged row groups'
@@ -1116,16 +1085,16 @@ static bool rtile_units_addressable(int64_t units, size_t vb)
 
 static void ensure_rtile(GB_Matrix_opaque *A)
 {
-    if (A->rt_state != 0) return;
-    A->rt_state = -1;
-    GB_Matrix_opaque *S = A->short_part;
+    if (A->split.rtile.rt_state != 0) return;
+    auto declined = [&]() { A->split.rtile.rt_state = -1; };  // not possible for this matrix (sizes, types)
+    GB_Matrix_opaque *S = A->split.short_part.get();
     const size_t vs = S->type->size;
     // (4- and 8-byte types with their values; BOOL matrices when they are iso -- the adjacency matrices of the BFS step: k_mxv_rtile_bool)
     const bool is_bool = S->type->code == TC_BOOL;
-    if (!S->d_col || S->nvals == 0 || S->nvals >= 0xf0000000ll || A->tg_state == 0) return;
-    if (is_bool ? !S->iso : (S->iso || (vs != 4 && vs != 8))) return;
+    if (!S->d_col || S->nvals == 0 || S->nvals >= 0xf0000000ll || A->split.tagged.tg_state == 0) return declined();
+    if (is_bool ? !S->iso : (S->iso || (vs != 4 && vs != 8))) return declined();
     const int64_t m = (int64_t)S->nrows;
-    const int64_t live_rows = A->hot_identity ? std::min<int64_t>(m, std::max<int64_t>(A->ord_live_rows, 1)) : m;
+    const int64_t live_rows = A->hot_identity ? std::min<int64_t>(m, std::max<int64_t>(A->order.ord_live_rows, 1)) : m;
     const int64_t G = ceil_div(live_rows, 64);  // (the groups the row kernels cover; the rows behind them are empty)
     const int64_t rows_end = std::min<int64_t>(G * 64, m);
     const int rows4 = ctx().rtile_rows == 16384 ? 16384 : 8192;
@@ -1141,7 +1110,7 @@ static void ensure_rtile(GB_Matrix_opaque *A)
     prim_exclusive_sum_i64(flag.p, tidx.p, G + 1);
     int64_t n_tiles = 0;
     d2h(&n_tiles, tidx.p + G, sizeof(int64_t));
-    if (n_tiles <= 0 || n_tiles > (1 << 24)) return;
+    if (n_tiles <= 0 || n_tiles > (1 << 24)) return declined();
     DevBuf<int32_t> g0(n_tiles);
     DevBuf<int64_t> e0(n_tiles), units(n_tiles + 1);
     hipLaunchKernelGGL(k_rtile_starts, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, ctx().stream, sptr, (const int64_t *)flag.p, (const int64_t *)tidx.p, G, g0.p, e0.p);
@@ -1152,28 +1121,29 @@ static void ensure_rtile(GB_Matrix_opaque *A)
     // (unit numbers are 28-bit offsets of the kernel's buffer loads -- and the kernel addresses a unit's values at byte u * RT_EPL * sizeof(value)
     //  with 32-bit arithmetic: 8-byte values wrap from 2^27 units on, inside a descriptor clamped to 0xfffffff0 bytes.  The
     //  tagged row groups run when the layout is not built.)
-    if (total_units <= 0 || total_units >= 0x0ffffff0ll) return;
+    if (total_units <= 0 || total_units >= 0x0ffffff0ll) return declined();
     {
-        const size_t vb_chk = (A->vdict_n > 0 && vs == 4) ? 1 : (is_bool ? 1 : vs);
-        if (!rtile_units_addressable(total_units, vb_chk)) return;
+        const size_t vb_chk = (A->vd.vdict_n > 0 && vs == 4) ? 1 : (is_bool ? 1 : vs);
+        if (!rtile_units_addressable(total_units, vb_chk)) return declined();
     }
+    GB_Matrix_opaque::RowTiles rt;
     RTile *tiles = (RTile *)dev_alloc(sizeof(RTile) * (size_t)n_tiles);
-    A->d_rt_tiles = tiles;
+    rt.d_rt_tiles.reset(tiles);
     hipLaunchKernelGGL(k_rtile_table, dim3((unsigned)ceil_div(n_tiles, 256)), dim3(256), 0, ctx().stream, (const int32_t *)g0.p, (const int64_t *)units.p, n_tiles, G, tiles);
     const size_t ents = (size_t)total_units * RT_EPL;
-    const bool dict = A->vdict_n > 0 && vs == 4;
+    const bool dict = A->vd.vdict_n > 0 && vs == 4;
     const size_t vb = dict ? 1 : vs;
     // (round 6: a dictionary-coded matrix with at most 2^24 columns keeps the value code in the top byte of the column word -- no value stream)
     // (the codes of a hot-coded matrix in natural order -- rows_tile = 2 -- index the image [table | u]: ncols + hot_k of them)
-    const int64_t n_codes = (int64_t)S->ncols + (A->hot_identity ? 0 : std::max<int64_t>(A->hot_k, 0));
+    const int64_t n_codes = (int64_t)S->ncols + (A->hot_identity ? 0 : std::max<int64_t>(A->hot.hot_k, 0));
     const bool pack = dict && !is_bool && ctx().rtile_pack && n_codes <= ((int64_t)1 << 24);
-    A->d_rt_col = (int32_t *)dev_alloc(sizeof(int32_t) * ents);
-    A->d_rt_tag = (uint16_t *)dev_alloc(sizeof(uint16_t) * ents);
-    A->d_rt_val = (is_bool || pack) ? nullptr : dev_alloc(vb * ents);
-    A->d_rt_counter = (unsigned int *)dev_alloc_zero(64);
-    GRB_HIP(hipMemsetAsync(A->d_rt_col, 0xff, sizeof(int32_t) * ents, ctx().stream));
-    if (A->d_rt_val) GRB_HIP(hipMemsetAsync(A->d_rt_val, 0, vb * ents, ctx().stream));
-    hipLaunchKernelGGL(k_rtile_pad_tags, dim3((unsigned)ceil_div((int64_t)ents, 256)), dim3(256), 0, ctx().stream, A->d_rt_tag, (int64_t)ents, (uint16_t)rows_cap);
+    rt.d_rt_col.reset((int32_t *)dev_alloc(sizeof(int32_t) * ents));
+    rt.d_rt_tag.reset((uint16_t *)dev_alloc(sizeof(uint16_t) * ents));
+    rt.d_rt_val.reset((is_bool || pack) ? nullptr : dev_alloc(vb * ents));
+    rt.d_rt_counter.reset((unsigned int *)dev_alloc_zero(64));
+    GRB_HIP(hipMemsetAsync(rt.d_rt_col, 0xff, sizeof(int32_t) * ents, ctx().stream));
+    if (rt.d_rt_val) GRB_HIP(hipMemsetAsync(rt.d_rt_val, 0, vb * ents, ctx().stream));
+    hipLaunchKernelGGL(k_rtile_pad_tags, dim3((unsigned)ceil_div((int64_t)ents, 256)), dim3(256), 0, ctx().stream, rt.d_rt_tag, (int64_t)ents, (uint16_t)rows_cap);
     {
         DevBuf<uint64_t> key(nnz), key2(nnz);
         DevBuf<uint32_t> pay(nnz), pay2(nnz);
@@ -1186,9 +1156,9 @@ static void ensure_rtile(GB_Matrix_opaque *A)
         GRB_DISPATCH_TYPE(S->type->code, T, {
             if constexpr (sizeof(T) == 4 || sizeof(T) == 8 || std::is_same<T, bool>::value) {
                 hipLaunchKernelGGL((k_rtile_place<T>), dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, ctx().stream, (const uint64_t *)key2.p, (const uint32_t *)pay2.p, nnz,
-                                   (const int64_t *)e0.p, (const RTile *)tiles, (const uint16_t *)rtag.p, (const T *)S->d_val, A->d_rt_col, A->d_rt_tag, (T *)A->d_rt_val,
-                                   dict ? (const unsigned long long *)A->d_vd_table : (const unsigned long long *)nullptr,
-                                   dict ? (const unsigned char *)A->d_vd_codes : (const unsigned char *)nullptr, is_bool ? 1 : 0, pack ? 1 : 0);
+                                   (const int64_t *)e0.p, (const RTile *)tiles, (const uint16_t *)rtag.p, (const T *)S->d_val, rt.d_rt_col, rt.d_rt_tag, (T *)rt.d_rt_val.get(),
+                                   dict ? (const unsigned long long *)A->vd.d_vd_table : (const unsigned long long *)nullptr,
+                                   dict ? (const unsigned char *)A->vd.d_vd_codes : (const unsigned char *)nullptr, is_bool ? 1 : 0, pack ? 1 : 0);
             }
         })
         sync_stream();  // (the temporaries are released at the end of this scope)
@@ -1199,13 +1169,14 @@ static void ensure_rtile(GB_Matrix_opaque *A)
     std::vector<int32_t> order((size_t)n_tiles);
     for (int64_t t = 0; t < n_tiles; t++) order[(size_t)t] = (int32_t)t;
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return h_tiles[(size_t)x].n_units > h_tiles[(size_t)y].n_units; });
-    A->d_rt_order = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)n_tiles);
-    h2d(A->d_rt_order, order.data(), sizeof(int32_t) * (size_t)n_tiles);
+    rt.d_rt_order.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)n_tiles));
+    h2d(rt.d_rt_order, order.data(), sizeof(int32_t) * (size_t)n_tiles);
     sync_stream();
-    A->rt_units = total_units;
-    A->rt_ntiles = (int)n_tiles;
-    A->rt_rows4 = rows4;
-    A->rt_state = 1;
+    rt.rt_units = total_units;
+    rt.rt_ntiles = (int)n_tiles;
+    rt.rt_rows4 = rows4;
+    rt.rt_state = 1;
+    A->split.rtile = std::move(rt);
 }
 
 template <typename T, int MON, int MUL, int IPT>
@@ -1214,20 +1185,20 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
     using W = typename Widen<T>::type;
     // long rows first (lean wavefront-per-chunk kernel straight from A's arrays), then the merge-path kernel over
     // the short part -- when the split exists and the operands are exactly A's own arrays (no typecast copy)
-    const bool use_split = A->split_state == 1 && a.aval == A->d_val &&
-                           a.col == (A->split_hot ? A->d_col_hot : A->d_col) && a.n_chunks > 0;
+    const bool use_split = A->split.split_state == 1 && a.aval == A->d_val &&
+                           a.col == (A->split.split_hot ? A->col_hot() : A->d_col) && a.n_chunks > 0;
     if (use_split) {
-        GB_Matrix_opaque *S = A->short_part;
+        GB_Matrix_opaque *S = A->split.short_part.get();
         // (ablation build GRB_STRIP_ABL & 32: one scratch slot per lane of every chunk)
-        DevBuf<W> tl_val((GRB_STRIP_ABL & 32) ? std::max<int64_t>(a.n_long, (A->strip_cb[A->strip_ncls > 0 ? A->strip_ncls : 0] + 1) * 64) : a.n_long);
+        DevBuf<W> tl_val((GRB_STRIP_ABL & 32) ? std::max<int64_t>(a.n_long, (A->split.strips.strip_cb[A->split.strips.strip_ncls > 0 ? A->split.strips.strip_ncls : 0] + 1) * 64) : a.n_long);
         DevBuf<unsigned char> tl_has(a.n_long);
-        const bool by_strip = (A->split_kind == 2 || A->split_kind == 4) && A->long_nnz > 0 && (A->strip_nseg > 0 || A->ct_units > 0);
+        const bool by_strip = (A->split.split_kind == 2 || A->split.split_kind == 4) && A->split.long_nnz > 0 && (A->split.strips.strip_nseg > 0 || A->split.cold.ct_units > 0);
         ctx().stats.long_entries = A->nvals - S->nvals;
-        ctx().stats.long_segments = by_strip ? A->strip_nseg : 0;
-        const bool by_class = A->split_kind == 1 && A->long_nnz > 0 && A->n_items > 0;
-        ctx().stats.long_kernel = by_strip ? A->split_kind : (by_class ? 1 : 0);
+        ctx().stats.long_segments = by_strip ? A->split.strips.strip_nseg : 0;
+        const bool by_class = A->split.split_kind == 1 && A->split.long_nnz > 0 && A->split.n_items > 0;
+        ctx().stats.long_kernel = by_strip ? A->split.split_kind : (by_class ? 1 : 0);
         // (round 6: the short part holds the cold entries of the long rows below tails_max_len entries -- the short-row kernels merge)
-        a.long_tails = A->tails_max_len > 0 ? 1 : 0;
+        a.long_tails = A->split.tails_max_len > 0 ? 1 : 0;
         ctx().stats.long_tails = a.long_tails;
         DevBuf<uint32_t> long_act((size_t)ceil_div(a.n_long, 64) * 2);
         a.long_act = long_act.p;
@@ -1235,24 +1206,24 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
         bool hot_fast = false;
         // (not for iso matrices: their padding entries would carry the one stored value instead of 0, and value (+) padding word must
         //  be the identity -- INT64_MAX + v wraps)
-        if constexpr (MON >= 0) hot_fast = hstrip_fast_semiring<T>(MON, MUL) && A->split_kind == 4 && by_strip && a.u_full && a.need_uval && a.need_aval && !a.a_iso;
+        if constexpr (MON >= 0) hot_fast = hstrip_fast_semiring<T>(MON, MUL) && A->split.split_kind == 4 && by_strip && a.u_full && a.need_uval && a.need_aval && !a.a_iso;
         if (hot_fast) {
             // (the fast kernel reads a class's records through a buffer descriptor with 32-bit offsets: every class below 2 GiB, records of
             //  the layout it is compiled for)
-            const int rec_ct = A->vdict_n > 0 ? 24 : 16 + 8 * (int)sizeof(T);
+            const int rec_ct = A->vd.vdict_n > 0 ? 24 : 16 + 8 * (int)sizeof(T);
             int64_t widest = 0;
-            for (int c = 0; c < A->strip_ncls + A->hub_ncls; c++) widest = std::max<int64_t>(widest, A->strip_cb[c + 1] - A->strip_cb[c]);
-            if (A->hrec_bytes != rec_ct || widest * 64 * (int64_t)A->hrec_bytes >= (1ll << 31)) hot_fast = false;
+            for (int c = 0; c < A->split.strips.strip_ncls + A->split.strips.hub_ncls; c++) widest = std::max<int64_t>(widest, A->split.strips.strip_cb[c + 1] - A->split.strips.strip_cb[c]);
+            if (A->split.strips.hrec_bytes != rec_ct || widest * 64 * (int64_t)A->split.strips.hrec_bytes >= (1ll << 31)) hot_fast = false;
         }
         DevBuf<unsigned char> long_act8(hot_fast && a.has_mask ? (size_t)a.n_long : 1);
         a.long_act8 = long_act8.p;
         // BOOL, a terminal monoid, the operand as pairs or presence bits: the first entries of every admitted long row are tested here
         LongProbe pb{nullptr, 0, nullptr, nullptr, nullptr, 0u};
         if constexpr (std::is_same<T, bool>::value && ((MON == OP_LOR && MUL == OP_LAND) || (MON == OP_ANY && MUL == OP_PAIR))) {
-            if (by_class && A->d_probe && ctx().bool_probe > 0 && !a.u_full && (a.u_pv != nullptr || !a.need_uval) && (a.a_iso || !a.need_aval) &&
-                a.col == (A->split_hot ? A->d_col_hot : A->d_col)) {
-                pb.probe = A->d_probe;
-                pb.k = std::min(ctx().bool_probe, A->probe_k);
+            if (by_class && A->split.d_probe && ctx().bool_probe > 0 && !a.u_full && (a.u_pv != nullptr || !a.need_uval) && (a.a_iso || !a.need_aval) &&
+                a.col == (A->split.split_hot ? A->col_hot() : A->d_col)) {
+                pb.probe = A->split.d_probe;
+                pb.k = std::min(ctx().bool_probe, A->split.probe_k);
                 pb.pv = a.u_pv;
                 pb.pbits = a.u_pv ? nullptr : (const uint32_t *)a.u_bits;
                 pb.iso_val = a.need_aval ? (const bool *)a.aval : nullptr;
@@ -1263,50 +1234,50 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
         hipLaunchKernelGGL((k_long_init<W>), dim3((unsigned)ceil_div(a.n_long, 256)), dim3(256), 0, ctx().stream, tl_val.p, tl_has.p,
                            a.n_long, pull_seed<T, W>(a, a.monoid), a.long_rows, a.m_bits, a.has_mask, a.m_comp, long_act.p,
                            ((by_class || by_strip) && a.u_full) ? 1 : 0, (by_strip && acc_is_ordered<W>(a.monoid)) ? 1 : 0,
-                           (hot_fast && a.has_mask) ? long_act8.p : nullptr, A->rt_state == 1 ? A->d_rt_counter : nullptr, pb);
+                           (hot_fast && a.has_mask) ? long_act8.p : nullptr, A->split.rtile.rt_state == 1 ? A->split.rtile.d_rt_counter.get() : nullptr, pb);
         a.tl_ord = (by_strip && acc_is_ordered<W>(a.monoid)) ? 1 : 0;
         a.long_has_known = ((by_class || by_strip) && a.u_full) ? 1 : 0;
         a.tl_val = tl_val.p;
         a.tl_has = tl_has.p;
         a.dbg = ctx().debug_flags;
-        const int64_t ncb = ceil_div(A->n_items, (int64_t)COMPACT_BLOCK);
+        const int64_t ncb = ceil_div(A->split.n_items, (int64_t)COMPACT_BLOCK);
         // (the items of the rows that are switched off -- by the mask, or decided by the bottom-up probe -- are compacted away per call)
         const bool compact = by_class && (a.has_mask || pb.probe != nullptr);
-        DevBuf<int64_t> act_start(compact ? (size_t)A->n_items : 1), block_cnt(compact ? (size_t)ncb + 1 : 1), class_off(9);
-        DevBuf<int32_t> act_len(compact ? (size_t)A->n_items : 1), act_slot(compact ? (size_t)A->n_items : 1);
+        DevBuf<int64_t> act_start(compact ? (size_t)A->split.n_items : 1), block_cnt(compact ? (size_t)ncb + 1 : 1), class_off(9);
+        DevBuf<int32_t> act_len(compact ? (size_t)A->split.n_items : 1), act_slot(compact ? (size_t)A->split.n_items : 1);
         if (by_strip) {
-            a.lcol = A->d_lcol;
-            a.lval = A->d_lval;
-            a.cls_lds_lim = A->cls_lds_lim;
-            a.strip_start = A->d_sstart;
-            a.strip_slot = A->d_sslot;
-            a.strip_slot16 = A->d_sslot16;  // (round 6: 16-bit offsets + a base per chunk; d_sslot is then gone)
-            a.strip_slot_base = A->d_sslot_base;
-            a.strip_nseg = A->strip_nseg;
-            for (int c = 0; c <= A->strip_ncls; c++) a.strip_cb[c] = A->strip_cb[c];
-            a.strip_ncls = A->strip_ncls;
-            const int64_t G = std::max<int64_t>(A->strip_ncls, (int64_t)(ctx().num_cus / A->strip_ncls) * A->strip_ncls);
-            if (A->split_kind == 4) {
+            a.lcol = A->split.d_lcol;
+            a.lval = A->split.d_lval;
+            a.cls_lds_lim = A->split.cls_lds_lim;
+            a.strip_start = A->split.strips.d_sstart;
+            a.strip_slot = A->split.strips.d_sslot;
+            a.strip_slot16 = A->split.strips.d_sslot16;  // (round 6: 16-bit offsets + a base per chunk; d_sslot is then gone)
+            a.strip_slot_base = A->split.strips.d_sslot_base;
+            a.strip_nseg = A->split.strips.strip_nseg;
+            for (int c = 0; c <= A->split.strips.strip_ncls; c++) a.strip_cb[c] = A->split.strips.strip_cb[c];
+            a.strip_ncls = A->split.strips.strip_ncls;
+            const int64_t G = std::max<int64_t>(A->split.strips.strip_ncls, (int64_t)(ctx().num_cus / A->split.strips.strip_ncls) * A->split.strips.strip_ncls);
+            if (A->split.split_kind == 4) {
                 // hot strips (lane records, LDS gathers only), then the cold strips (image gathers) with a token LDS array
-                a.hrec = A->d_hrec;
-                a.hrec_bytes = A->hrec_bytes;
-                a.vdict = A->vdict_n > 0 ? A->d_vdict : nullptr;
-                ctx().stats.value_dict = A->vdict_n;
+                a.hrec = A->split.strips.d_hrec;
+                a.hrec_bytes = A->split.strips.hrec_bytes;
+                a.vdict = A->vd.vdict_n > 0 ? A->vd.d_vdict.get() : nullptr;
+                ctx().stats.value_dict = A->vd.vdict_n;
                 // the cold entries (tagged tiles, column range by column range per XCD) gather through the texture path and leave HBM idle; the hot
                 // strips stream from HBM and leave the texture path idle; both only ADD to the long rows' accumulators (atomics), so their order
                 // does not matter.  They run one after the other on the library's stream, before the short-row kernel that reads the accumulators
                 // (two streams were measured to change nothing: docs/HISTORY.md)
                 auto launch_ctile = [&]() {
-                    if (A->ct_units <= 0) return;
-                    a.ct_col = A->d_ct_col;
-                    a.ct_val = A->d_ct_val;
-                    a.ct_loc = A->d_ct_loc;
-                    a.ct_tiles = (const CTile *)A->d_ct_tiles;
-                    a.ct_mode = A->ct_mode;
-                    a.ct_cbase = A->ct_mode ? (const int32_t *)((const char *)A->d_ct_tiles + sizeof(CTile) * (size_t)std::max<int64_t>(A->ct_ntiles, 1)) : nullptr;
-                    if (A->ct_mode == 2) a.vdict = A->d_vdict;  // (the cold tiles' values are dictionary codes)
-                    a.ct_order = A->d_ct_order;
-                    for (int x = 0; x <= 8; x++) a.ct_xoff[x] = A->ct_xoff[x];
+                    if (A->split.cold.ct_units <= 0) return;
+                    a.ct_col = A->split.cold.d_ct_col;
+                    a.ct_val = A->split.cold.d_ct_val;
+                    a.ct_loc = A->split.cold.d_ct_loc;
+                    a.ct_tiles = (const CTile *)A->split.cold.d_ct_tiles.get();
+                    a.ct_mode = A->split.cold.ct_mode;
+                    a.ct_cbase = A->split.cold.ct_mode ? (const int32_t *)((const char *)A->split.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(A->split.cold.ct_ntiles, 1)) : nullptr;
+                    if (A->split.cold.ct_mode == 2) a.vdict = A->vd.d_vdict;  // (the cold tiles' values are dictionary codes)
+                    a.ct_order = A->split.cold.d_ct_order;
+                    for (int x = 0; x <= 8; x++) a.ct_xoff[x] = A->split.cold.ct_xoff[x];
                     const int64_t Gt = std::max<int64_t>(8, (int64_t)(ctx().num_cus * CT_WGS_PER_CU / 8) * 8);
                     hipLaunchKernelGGL((k_mxv_ctile<T, MON, MUL>), dim3((unsigned)Gt), dim3(CT_BLOCK), 0, ctx().stream, a);
                     ctx().stats.kernel_launches += 1;
@@ -1315,36 +1286,36 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
                 bool merged = false;
                 if constexpr (MON >= 0) {
                     if constexpr (hstrip_fast_semiring<T>(MON, MUL)) {
-                        if (hot_fast && A->hub_ncls > 0 && A->d_wg_tab && A->wg_tab_g > 0 && A->strip_cb[A->strip_ncls + A->hub_ncls] > 0) {
+                        if (hot_fast && A->split.strips.hub_ncls > 0 && A->split.strips.d_wg_tab && A->split.strips.wg_tab_g > 0 && A->split.strips.strip_cb[A->split.strips.strip_ncls + A->split.strips.hub_ncls] > 0) {
                             PullArgs al = a;
-                            al.wg_tab = A->d_wg_tab;
-                            al.strip_cb_dev = A->d_strip_cb;
-                            al.strip_chunks = A->strip_cb[A->strip_ncls + A->hub_ncls];
+                            al.wg_tab = A->split.strips.d_wg_tab;
+                            al.strip_cb_dev = A->split.strips.d_strip_cb;
+                            al.strip_chunks = A->split.strips.strip_cb[A->split.strips.strip_ncls + A->split.strips.hub_ncls];
                             bool dict_launched = false;
                             const bool s16 = al.strip_slot16 != nullptr;
                             if constexpr (sizeof(T) == 4) {
                                 if (al.vdict) {
-                                    if (s16) hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, true, true>), dim3((unsigned)A->wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
-                                    else hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, true>), dim3((unsigned)A->wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
+                                    if (s16) hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, true, true>), dim3((unsigned)A->split.strips.wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
+                                    else hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, true>), dim3((unsigned)A->split.strips.wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
                                     dict_launched = true;
                                 }
                             }
                             if (!dict_launched) {
-                                if (s16) hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, false, true>), dim3((unsigned)A->wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
-                                else hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS>), dim3((unsigned)A->wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
+                                if (s16) hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS, false, true>), dim3((unsigned)A->split.strips.wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
+                                else hipLaunchKernelGGL((k_mxv_hstrip<T, MON, MUL, LONG_LDS_WORDS>), dim3((unsigned)A->split.strips.wg_tab_g), dim3(LONG_BLOCK), 0, ctx().stream, al);
                             }
                             merged = true;
                         }
                     }
                 }
                 // otherwise level 0: the classes of all long rows; level 1 (an ordered matrix): the 64 classes of its hub rows, strip_cb[strip_ncls ..]
-                for (int level = 0; !merged && level < (A->hub_ncls > 0 ? 2 : 1); level++) {
-                    const int c0 = level ? A->strip_ncls : 0, nc = level ? A->hub_ncls : A->strip_ncls;
-                    if (A->strip_cb[c0 + nc] == A->strip_cb[c0]) continue;  // (no chunk at this level)
+                for (int level = 0; !merged && level < (A->split.strips.hub_ncls > 0 ? 2 : 1); level++) {
+                    const int c0 = level ? A->split.strips.strip_ncls : 0, nc = level ? A->split.strips.hub_ncls : A->split.strips.strip_ncls;
+                    if (A->split.strips.strip_cb[c0 + nc] == A->split.strips.strip_cb[c0]) continue;  // (no chunk at this level)
                     PullArgs al = a;
                     al.strip_ncls = nc;
-                    for (int c = 0; c <= nc; c++) al.strip_cb[c] = A->strip_cb[c0 + c];
-                    al.cls_lds_lim = level ? A->hub_lds_lim : A->cls_lds_lim;
+                    for (int c = 0; c <= nc; c++) al.strip_cb[c] = A->split.strips.strip_cb[c0 + c];
+                    al.cls_lds_lim = level ? A->split.strips.hub_lds_lim : A->split.cls_lds_lim;
                     const int64_t Gl = std::max<int64_t>(nc, (int64_t)(ctx().num_cus / nc) * nc);
                     bool launched = false;
                     if constexpr (MON >= 0) {
@@ -1375,21 +1346,21 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
             } else
             hipLaunchKernelGGL((k_mxv_strip<T, MON, MUL, LONG_LDS_WORDS>), dim3((unsigned)G), dim3(LONG_BLOCK), 0, ctx().stream, a);
         } else if (by_class) {
-            a.lcol = A->d_lcol;
-            a.lval = A->d_lval;
-            a.it_start = A->d_it_start;
-            a.it_len = A->d_it_len;
-            a.it_slot = A->d_it_slot;
-            for (int c = 0; c < 9; c++) a.item_begin[c] = A->item_begin[c];
-            a.cls_lds_lim = A->cls_lds_lim;
+            a.lcol = A->split.d_lcol;
+            a.lval = A->split.d_lval;
+            a.it_start = A->split.d_it_start;
+            a.it_len = A->split.d_it_len;
+            a.it_slot = A->split.d_it_slot;
+            for (int c = 0; c < 9; c++) a.item_begin[c] = A->split.item_begin[c];
+            a.cls_lds_lim = A->split.cls_lds_lim;
             a.class_off = nullptr;
             if (compact) {
-                hipLaunchKernelGGL(k_long_compact_count, dim3((unsigned)ncb), dim3(256), 0, ctx().stream, (const int32_t *)A->d_it_slot,
-                                   A->n_items, (const uint32_t *)long_act.p, block_cnt.p);
+                hipLaunchKernelGGL(k_long_compact_count, dim3((unsigned)ncb), dim3(256), 0, ctx().stream, (const int32_t *)A->split.d_it_slot,
+                                   A->split.n_items, (const uint32_t *)long_act.p, block_cnt.p);
                 prim_exclusive_sum_i64(block_cnt.p, block_cnt.p, ncb + 1);
-                hipLaunchKernelGGL(k_long_compact_write, dim3((unsigned)ncb), dim3(256), 0, ctx().stream, (const int32_t *)A->d_it_slot,
-                                   A->n_items, (const uint32_t *)long_act.p, (const int64_t *)block_cnt.p,
-                                   (const int64_t *)A->d_item_begin, (const int64_t *)A->d_it_start, (const int32_t *)A->d_it_len,
+                hipLaunchKernelGGL(k_long_compact_write, dim3((unsigned)ncb), dim3(256), 0, ctx().stream, (const int32_t *)A->split.d_it_slot,
+                                   A->split.n_items, (const uint32_t *)long_act.p, (const int64_t *)block_cnt.p,
+                                   (const int64_t *)A->split.d_item_begin, (const int64_t *)A->split.d_it_start, (const int32_t *)A->split.d_it_len,
                                    act_start.p, act_len.p, act_slot.p, class_off.p);
                 a.it_start = act_start.p;
                 a.it_len = act_len.p;
@@ -1403,7 +1374,7 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
         } else if (a.long_tails) {
             // (neither strips nor cold tiles were built.  With cold entries of long rows in the short part that means EVERY entry of every long row
             //  is there -- hub rows, which keep theirs, always produce strips or tiles -- and the chunk kernel, which walks whole rows of A, must not run)
-            if (A->long_nnz > 0) fail(GrB_PANIC, "pull SpMV: long rows with entries in the short part but no strips (internal error)");
+            if (A->split.long_nnz > 0) fail(GrB_PANIC, "pull SpMV: long rows with entries in the short part but no strips (internal error)");
         } else {
             const int64_t want = ceil_div(a.n_chunks, LONG_BLOCK / 64);
             const int64_t G = std::min<int64_t>(want, (int64_t)ctx().num_cus);  // persistent: one 1024-thread workgroup per CU
@@ -1415,24 +1386,24 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
         b.col = S->d_col;
         b.aval = S->d_val;
         b.nnz = S->nvals;
-        b.long_bits = A->d_long_bits;
+        b.long_bits = A->split.d_long_bits;
         b.n_chunks = 0;
         b.n_long_epi = a.n_long;
         const int sk = short_kernel_for(A);
-        if ((sk == 5 || A->short_tagged_only) && S->nrows == A->nrows && S->nvals < 0x1ffffffffll) {
+        if ((sk == 5 || A->split.short_tagged_only) && S->nrows == A->nrows && S->nvals < 0x1ffffffffll) {
             // short rows as tagged row groups: the row of every entry is stored with it (no marks, no scan, no segmented fold)
             // (round 6: the groups' offsets and non-empty words now, their entries only if the call ends up with k_mxv_rows_tag -- lazy_tagged)
             ensure_tagged_index(A);
-            b.long_prefix = A->d_long_prefix;
-            b.tg_off = A->d_tg_off;
-            b.vdict = A->vdict_n > 0 ? A->d_vdict : nullptr;
-            b.tg_nonempty = A->d_tg_nonempty;
+            b.long_prefix = A->split.d_long_prefix;
+            b.tg_off = A->split.tagged.d_tg_off;
+            b.vdict = A->vd.vdict_n > 0 ? A->vd.d_vdict.get() : nullptr;
+            b.tg_nonempty = A->split.tagged.d_tg_nonempty;
             int64_t groups = ceil_div(b.m, 64);
             b.tg_groups = 0;
             b.tg_stride = 0;
             if (A->hot_identity) {
                 // a matrix in its popularity order: rows sorted by falling weight, the empty ones at the end
-                const int64_t live_groups = std::max<int64_t>(1, ceil_div(A->ord_live_rows, 64));
+                const int64_t live_groups = std::max<int64_t>(1, ceil_div(A->order.ord_live_rows, 64));
                 // (an output written into fresh buffers keeps its tail in the kernel: the values move too -- unless nothing of the tail survives
                 //  the call: replace without an accumulator, the level step of a BFS whose frontier is its own output)
                 const bool tail_dies = b.replace && b.accum < 0;
@@ -1454,21 +1425,21 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
             // the sorted row tiles of an ordered matrix (round 5, grb_mxv_rtile.inc): a specialised semiring over a full operand (or an image
             // with the absorbing value under its absent entries) whose values are read, values of the matrix read, output in place
             if constexpr (MON >= 0 && !std::is_same<T, bool>::value && (sizeof(T) == 4 || sizeof(T) == 8)) {
-                if (ctx().rows_tile && A->rt_state == 1 && b.u_full && b.need_uval && b.need_aval && !b.a_iso &&
-                    (A->hot_identity ? (b.tg_groups > 0 && b.tg_groups == ceil_div(std::min<int64_t>(b.m, std::max<int64_t>(A->ord_live_rows, 1)), 64)) : b.tg_groups == 0) &&
+                if (ctx().rows_tile && A->split.rtile.rt_state == 1 && b.u_full && b.need_uval && b.need_aval && !b.a_iso &&
+                    (A->hot_identity ? (b.tg_groups > 0 && b.tg_groups == ceil_div(std::min<int64_t>(b.m, std::max<int64_t>(A->order.ord_live_rows, 1)), 64)) : b.tg_groups == 0) &&
                     b.m * (int64_t)sizeof(T) < 0xfffffff0ll) {  // (the old values of a tile's rows are read through a buffer descriptor)
-                    b.rt_col = A->d_rt_col;
-                    b.rt_tag = A->d_rt_tag;
-                    b.rt_val = A->d_rt_val;
-                    b.rt_tiles = (const RTile *)A->d_rt_tiles;
-                    b.rt_order = A->d_rt_order;
-                    b.rt_counter = A->d_rt_counter;
-                    b.rt_units = A->rt_units;
-                    b.rt_ntiles = A->rt_ntiles;
+                    b.rt_col = A->split.rtile.d_rt_col;
+                    b.rt_tag = A->split.rtile.d_rt_tag;
+                    b.rt_val = A->split.rtile.d_rt_val;
+                    b.rt_tiles = (const RTile *)A->split.rtile.d_rt_tiles.get();
+                    b.rt_order = A->split.rtile.d_rt_order;
+                    b.rt_counter = A->split.rtile.d_rt_counter;
+                    b.rt_units = A->split.rtile.rt_units;
+                    b.rt_ntiles = A->split.rtile.rt_ntiles;
                     const bool dict = b.vdict != nullptr && sizeof(T) == 4;
-                    const bool pack = dict && A->d_rt_val == nullptr;  // (value codes in the top byte of the column words: ensure_rtile)
-                    const bool tall = A->rt_rows4 == 16384;
-                    const int64_t G = std::min<int64_t>(A->rt_ntiles, (int64_t)ctx().num_cus * (tall ? 2 : 4));
+                    const bool pack = dict && A->split.rtile.d_rt_val == nullptr;  // (value codes in the top byte of the column words: ensure_rtile)
+                    const bool tall = A->split.rtile.rt_rows4 == 16384;
+                    const int64_t G = std::min<int64_t>(A->split.rtile.rt_ntiles, (int64_t)ctx().num_cus * (tall ? 2 : 4));
                     bool launched = false;
                     if constexpr (sizeof(T) == 4) {
                         if (dict && pack) {
@@ -1488,38 +1459,38 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
                     GRB_HIP(hipGetLastError());
                     ctx().stats.kernel_launches += 1;
                     ctx().stats.fused_epilogue = 3;  // (bookkeeping: 3 = fused, by the sorted row tiles)
-                    ctx().stats.tiles = A->rt_ntiles;
+                    ctx().stats.tiles = A->split.rtile.rt_ntiles;
                     return;
                 }
             }
             // ... and BOOL products over an operand given as presence / value pairs (the BFS level step): k_mxv_rtile_bool
             if constexpr (std::is_same<T, bool>::value && ((MON == OP_LOR && MUL == OP_LAND) || (MON == OP_ANY && MUL == OP_PAIR))) {
-                if (ctx().rows_tile && A->rt_state == 1 && !b.u_full && (b.u_pv != nullptr || !b.need_uval) && (b.a_iso || !b.need_aval) &&
-                    (A->hot_identity ? (b.tg_groups > 0 && b.tg_groups == ceil_div(std::min<int64_t>(b.m, std::max<int64_t>(A->ord_live_rows, 1)), 64)) : b.tg_groups == 0) &&
+                if (ctx().rows_tile && A->split.rtile.rt_state == 1 && !b.u_full && (b.u_pv != nullptr || !b.need_uval) && (b.a_iso || !b.need_aval) &&
+                    (A->hot_identity ? (b.tg_groups > 0 && b.tg_groups == ceil_div(std::min<int64_t>(b.m, std::max<int64_t>(A->order.ord_live_rows, 1)), 64)) : b.tg_groups == 0) &&
                     b.m < 0xfffffff0ll) {
-                    b.rt_col = A->d_rt_col;
-                    b.rt_tag = A->d_rt_tag;
+                    b.rt_col = A->split.rtile.d_rt_col;
+                    b.rt_tag = A->split.rtile.d_rt_tag;
                     b.rt_val = nullptr;
-                    b.rt_tiles = (const RTile *)A->d_rt_tiles;
-                    b.rt_order = A->d_rt_order;
-                    b.rt_counter = A->d_rt_counter;
-                    b.rt_units = A->rt_units;
-                    b.rt_ntiles = A->rt_ntiles;
-                    const int64_t G = std::min<int64_t>(A->rt_ntiles, (int64_t)ctx().num_cus * 4);
-                    if (A->rt_rows4 == 16384) hipLaunchKernelGGL((k_mxv_rtile_bool<MON, MUL, 16384>), dim3((unsigned)G), dim3(RT_BLOCK), 0, ctx().stream, b);
+                    b.rt_tiles = (const RTile *)A->split.rtile.d_rt_tiles.get();
+                    b.rt_order = A->split.rtile.d_rt_order;
+                    b.rt_counter = A->split.rtile.d_rt_counter;
+                    b.rt_units = A->split.rtile.rt_units;
+                    b.rt_ntiles = A->split.rtile.rt_ntiles;
+                    const int64_t G = std::min<int64_t>(A->split.rtile.rt_ntiles, (int64_t)ctx().num_cus * 4);
+                    if (A->split.rtile.rt_rows4 == 16384) hipLaunchKernelGGL((k_mxv_rtile_bool<MON, MUL, 16384>), dim3((unsigned)G), dim3(RT_BLOCK), 0, ctx().stream, b);
                     else hipLaunchKernelGGL((k_mxv_rtile_bool<MON, MUL, 8192>), dim3((unsigned)G), dim3(RT_BLOCK), 0, ctx().stream, b);
                     GRB_HIP(hipGetLastError());
                     ctx().stats.kernel_launches += 1;
                     ctx().stats.fused_epilogue = 3;
-                    ctx().stats.tiles = A->rt_ntiles;
+                    ctx().stats.tiles = A->split.rtile.rt_ntiles;
                     return;
                 }
             }
             // (neither kind of row tiles took the call: the tagged row groups -- their entries laid out now if they were not yet)
             ensure_tagged(A);
-            b.tg_col = A->d_tg_col;
-            b.tg_val = A->d_tg_val;
-            b.tg_tag = A->d_tg_tag;
+            b.tg_col = A->split.tagged.d_tg_col;
+            b.tg_val = A->split.tagged.d_tg_val;
+            b.tg_tag = A->split.tagged.d_tg_tag;
             bool head = false;
             if constexpr (MON >= 0 && std::is_same<T, bool>::value) {
                 head = ctx().rows_head && A->hot_identity && b.tg_stride > 0 && b.u_pv != nullptr && groups >= ctx().rows_head_min_groups;
@@ -1540,7 +1511,7 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
         if (a.long_tails) fail(GrB_PANIC, "pull SpMV: the short part holds entries of long rows, which only the tagged row groups and the row tiles merge (internal error)");
         if (sk != 0 && S->nrows == A->nrows) {
             // short rows: one wavefront per 64 consecutive rows, which also applies the write rule of the long rows
-            b.long_prefix = A->d_long_prefix;
+            b.long_prefix = A->split.d_long_prefix;
             // (persistent variants -- static strides with the next group prefetched, or an LDS work counter per workgroup --
             //  measured 3-10 % slower than one group per wavefront)
             hipLaunchKernelGGL((k_mxv_rows<T, MON, MUL>), dim3((unsigned)ceil_div(ceil_div(b.m, 64), ROWS_BLOCK / 64)), dim3(ROWS_BLOCK), 0,
@@ -1557,8 +1528,8 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
     constexpr int TILE = PULL_BLOCK * IPT;
     a.dbg = ctx().debug_flags;
     ensure_tile_table(A, TILE);
-    a.tile_row = A->d_tile_row;
-    a.n_tiles = A->n_tiles;
+    a.tile_row = A->tile.d_tile_row;
+    a.n_tiles = A->tile.n_tiles;
     if (a.n_tiles > 0x7fffffff) fail(GrB_NOT_IMPLEMENTED, "too many tiles for one launch");
     DevBuf<W> carry_val(a.n_tiles), first_val(a.n_tiles);
     DevBuf<uint8_t> carry_has(a.n_tiles), first_has(a.n_tiles);
@@ -1744,20 +1715,20 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     DevBuf<uint64_t> xcat_bits(0);
     // the first pull over a large matrix runs on the CSR arrays as they are; the layouts below (tens of milliseconds to build at
     // scale 24) are built when the matrix comes back for a second product
-    const bool lazy = ctx().lazy_layout && S->nvals >= ctx().lazy_min_nnz && S->pull_calls == 0 && S->hot_state == 0 && S->split_state == 0;
+    const bool lazy = ctx().lazy_layout && S->nvals >= ctx().lazy_min_nnz && S->pull_calls == 0 && S->hot.hot_state == 0 && S->split.split_state == 0;
     S->pull_calls++;
     if (S->hot_identity) {
         // a matrix in its popularity order (grb_mxv_order.inc): the column codes are positions of the operand itself -- the first hot_k of
         // them are the hot table, nothing is gathered per call
-        a.col = S->d_col_hot;
-        ctx().stats.hot_k = S->hot_k;
+        a.col = S->col_hot();
+        ctx().stats.hot_k = S->hot.hot_k;
     } else if ((a.need_uval || !a.u_full) && !lazy) {
         ensure_hot(S, type_size(st));
         // (once the split is built from the re-coded columns, the re-coded copy of the WHOLE column array is released --
         //  1.05 GB of the 3.7 GB of layouts at scale 24: a call that cannot take the split then runs on the plain arrays)
         const bool split_usable = S->nvals && (S->type->code == st || !need_aval) && !by_rowlen;
-        if (S->hot_state == 1 && (!S->hot_cols_dropped || split_usable) && (uint64_t)(u->n + S->hot_k) * type_size(st) < 0xff000000ull) {
-            const int k = (int)S->hot_k;  // multiple of 64
+        if (S->hot.hot_state == 1 && (!S->hot.hot_cols_dropped || split_usable) && (uint64_t)(u->n + S->hot.hot_k) * type_size(st) < 0xff000000ull) {
+            const int k = (int)S->hot.hot_k;  // multiple of 64
             const size_t vb = type_size(st);
             char *img_val;
             uint64_t *img_bits;
@@ -1768,7 +1739,7 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
                 img_bits = u->d_bits - k / 64;
                 GRB_DISPATCH_TYPE(st, T, {
                     hipLaunchKernelGGL((k_x_image<T>), dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, ctx().stream,
-                                       (const int32_t *)S->d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits, a.u_full,
+                                       (const int32_t *)S->hot.d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits, a.u_full,
                                        (T *)img_val, img_bits, (int64_t)u->n);
                 })
             } else {
@@ -1782,13 +1753,13 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
                 if (((uintptr_t)uval & 15u) == 0) {
                     GRB_DISPATCH_TYPE(st, T, {
                         hipLaunchKernelGGL((k_x_image<T>), dim3((unsigned)(ceil_div(k, 256) + ceil_div(copy_threads, 256))), dim3(256), 0,
-                                           ctx().stream, (const int32_t *)S->d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits,
+                                           ctx().stream, (const int32_t *)S->hot.d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits,
                                            a.u_full, (T *)img_val, img_bits, (int64_t)u->n);
                     })
                 } else {  // (a typecast copy of u need not be 16-byte aligned)
                     GRB_DISPATCH_TYPE(st, T, {
                         hipLaunchKernelGGL((k_x_image<T>), dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, ctx().stream,
-                                           (const int32_t *)S->d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits, a.u_full,
+                                           (const int32_t *)S->hot.d_hot_cols, k, (const T *)uval, (const uint32_t *)u->d_bits, a.u_full,
                                            (T *)img_val, img_bits, (int64_t)u->n);
                     })
                     d2d(img_val + vb * (size_t)k, uval, vb * (size_t)u->n);
@@ -1797,7 +1768,7 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
             }
             ctx().stats.kernel_launches += 1;
             ctx().stats.hot_k = k;
-            a.col = S->d_col_hot;
+            a.col = S->col_hot();
             a.u_val = img_val;
             a.u_bits = (const uint32_t *)img_bits;
             a.x_len = (int64_t)u->n + k;
@@ -1805,7 +1776,7 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     }
     // long/short row split (large matrices whose long rows hold a good share of the entries)
     if (S->nvals && (S->type->code == st || !need_aval) && !by_rowlen && !lazy) {
-        bool hot = (a.col == S->d_col_hot);
+        bool hot = (a.col == S->col_hot());
         // An existing split is never rebuilt because a call comes with the other column coding (mixing row reductions and
         // products on one matrix used to rebuild the layouts -- tens of milliseconds at scale 24 -- at every call, and a
         // rebuild after the re-coded columns were released read a null column array): a call that reads no column at all (a
@@ -1813,22 +1784,22 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
         // with the original column indices while the split holds table codes runs on the plain arrays.  Only a split in the
         // original coding is replaced when a call can use the hot table.
         const bool reads_cols = a.need_uval || !a.u_full;
-        if (S->split_state == 1 && S->split_hot != hot && !reads_cols) {
-            hot = S->split_hot;
-            a.col = hot ? S->d_col_hot : S->d_col;
-        } else if (S->split_state == 1 && S->split_hot && !hot) {
+        if (S->split.split_state == 1 && S->split.split_hot != hot && !reads_cols) {
+            hot = S->split.split_hot;
+            a.col = hot ? S->col_hot() : S->d_col;
+        } else if (S->split.split_state == 1 && S->split.split_hot && !hot) {
             // (plain path below: a.col is the original column array, which use_split does not match)
         } else {
             ensure_split(S, a.col, hot);
         }
-        if (hot && S->hot_cols_dropped) a.col = S->d_col_hot;  // (released when the split was built: the tag of the re-coded columns is now nullptr)
-        if (S->split_state == 1 && S->split_hot == hot) {
-            a.long_rows = S->d_long_rows;
-            a.chunk_slot = S->d_chunk_slot;
-            a.chunk_start = S->d_chunk_start;
-            a.chunk_len = S->d_chunk_len;
-            a.n_chunks = S->n_chunks;
-            a.n_long = S->n_long;
+        if (hot && S->hot.hot_cols_dropped) a.col = S->col_hot();  // (released when the split was built: the tag of the re-coded columns is now nullptr)
+        if (S->split.split_state == 1 && S->split.split_hot == hot) {
+            a.long_rows = S->split.d_long_rows;
+            a.chunk_slot = S->split.d_chunk_slot;
+            a.chunk_start = S->split.d_chunk_start;
+            a.chunk_len = S->split.d_chunk_len;
+            a.n_chunks = S->split.n_chunks;
+            a.n_long = S->split.n_long;
         }
     }
     // A sparse operand of a floating-point min_plus / max_plus product on an ordered matrix: run it as a FULL operand whose absent entries
@@ -1839,9 +1810,9 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     // 1.53 to ~0.8 ms (section 4.1.10)
     DevBuf<char> fill_img(0);
     // (vals_finite comes with the dictionary, i.e. with FP32 today; the bound on the operand keeps every product finite)
-    const double fill_limit = (st == TC_FP32 ? 3.4028234663852886e38 : 1.7976931348623157e308) - S->vals_absmax;
-    if (S->hot_identity && !a.u_full && a.need_uval && ctx().fill_absent && S->vals_finite && fill_limit > 0 && !S->iso && (st == TC_FP32 || st == TC_FP64) &&
-        mult == OP_PLUS && (monoid == OP_MIN || monoid == OP_MAX) && S->split_state == 1 && S->split_kind == 4) {
+    const double fill_limit = (st == TC_FP32 ? 3.4028234663852886e38 : 1.7976931348623157e308) - S->vd.vals_absmax;
+    if (S->hot_identity && !a.u_full && a.need_uval && ctx().fill_absent && S->vd.vals_finite && fill_limit > 0 && !S->iso && (st == TC_FP32 || st == TC_FP64) &&
+        mult == OP_PLUS && (monoid == OP_MIN || monoid == OP_MAX) && S->split.split_state == 1 && S->split.split_kind == 4) {
         dev_free(fill_img.p);
         fill_img.p = (char *)dev_alloc(type_size(st) * (size_t)u->n);
         DevBuf<int> flag(1, true);
@@ -1865,7 +1836,7 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     DevBuf<uint64_t> valbits(0);
     // (u not full: presence and value share one word per 16 codes, one gather per entry instead of two -- every pull kernel
     //  but the chunk kernel of the long rows reads that form)
-    const bool chunk_kernel = S->split_state == 1 && !((S->split_kind == 1 || S->split_kind == 2 || S->split_kind == 4) && S->long_nnz > 0);
+    const bool chunk_kernel = S->split.split_state == 1 && !((S->split.split_kind == 1 || S->split.split_kind == 2 || S->split.split_kind == 4) && S->split.long_nnz > 0);
     if (st == TC_BOOL && a.need_uval && !a.u_full && !chunk_kernel && !(ctx().debug_flags & 2048)) {
         const int64_t len = a.x_len;
         dev_free(valbits.p);
@@ -2244,28 +2215,28 @@ static void mxv_any_order(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
     }
     // (a matrix with ranked labels, GrX_Matrix_hint_ranked: the ordered layouts without an order -- any shape, pinned vectors welcome)
     // (a row block with a column order, GrX_Matrix_shard_setup: only the operand is converted -- it must be free to: not pinned, not the output)
-    const bool col_only = S->col_order_only && S->perm && !S->ranked;
+    const bool col_only = S->order.col_order_only && S->order.perm && !S->ranked;
     if (shapes_ok && ctx().order_mode && S->nvals >= ctx().order_min_nnz && sr->type == S->type->code && S->d_col &&
         (S->ranked || (col_only ? (!u->pinned && u != w && u != mask && !u_token) : (S->nrows == S->ncols && !w->pinned && !u->pinned && !(mask && mask->pinned))))) {
         int mult = canonical_op(sr->type, sr->mult);
         if (flip) mult = flip_op(mult);
         const bool by_rowlen = mult == OP_PAIR && u->nvals == (int64_t)u->n && !(ctx().debug_flags & 65536);
         // (the first product of a large matrix runs on its arrays as they are -- lazy layouts, section 4.1.6 -- and counts itself)
-        const bool first = ctx().lazy_layout && S->nvals >= ctx().lazy_min_nnz && S->pull_calls == 0 && S->ord_state == 0;
+        const bool first = ctx().lazy_layout && S->nvals >= ctx().lazy_min_nnz && S->pull_calls == 0 && S->order.ord_state == 0;
         if (!by_rowlen && !first) {
             ensure_ordered(S);
-            ordered = S->ord_state == 1;
+            ordered = S->order.ord_state == 1;
         }
     }
     if (ordered && col_only) {
         // the operand in the column order, the output and the mask (the block's ROW space) natural
         vector_set_order(w, nullptr);
         if (mask) vector_set_order(mask, nullptr);
-        vector_set_order(u, S->perm);
-        mxv_core(w, mask, accum, sr, S->ord, u, flip, f);
+        vector_set_order(u, S->order.perm);
+        mxv_core(w, mask, accum, sr, S->order.ord, u, flip, f);
         ctx().stats.ordered = 1;
     } else if (ordered) {
-        GB_Perm *P = S->ranked ? nullptr : S->perm;  // (ranked labels: the twin is in the caller's own order -- the vectors stay natural)
+        GB_Perm *P = S->ranked ? nullptr : S->order.perm;  // (ranked labels: the twin is in the caller's own order -- the vectors stay natural)
         // an output that keeps nothing of its old content needs no conversion: it is emptied and takes the order
         const bool w_dead = !accum && (!mask || f.replace) && w != u && w != mask;
         if (w_dead && w->order != P && w->d_val) {
@@ -2274,7 +2245,7 @@ static void mxv_any_order(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
         }
         for (GB_Vector_opaque *v : vs)
             if (v) vector_set_order(v, P);
-        mxv_core(w, mask, accum, sr, S->ord, u, flip, f);
+        mxv_core(w, mask, accum, sr, S->order.ord, u, flip, f);
         ctx().stats.ordered = 1;
     } else {
         for (GB_Vector_opaque *v : vs)
@@ -2348,18 +2319,18 @@ extern "C" GrB_Info GrX_Matrix_hint_ranked(GrB_Matrix A, int ranked)
     require_init();
     check_matrix(A, "A");
     if (A->ranked != (ranked != 0)) {
-        if (A->ord) {
-            matrix_free(A->ord);
-            A->ord = nullptr;
+        if (A->order.ord) {
+            matrix_free(A->order.ord);
+            A->order.ord = nullptr;
         }
-        A->ord_state = 0;
+        A->order.ord_state = 0;
         A->ranked = ranked != 0;
         if (A->tr) {  // (the cached transpose shares the labels)
-            if (A->tr->ord) {
-                matrix_free(A->tr->ord);
-                A->tr->ord = nullptr;
+            if (A->tr->order.ord) {
+                matrix_free(A->tr->order.ord);
+                A->tr->order.ord = nullptr;
             }
-            A->tr->ord_state = 0;
+            A->tr->order.ord_state = 0;
             A->tr->ranked = A->ranked;
         }
     }
@@ -2381,8 +2352,8 @@ extern "C" GrB_Info GrX_Matrix_shard_setup(GrB_Matrix A, const uint32_t *col_cou
     const int64_t n = (int64_t)A->ncols;
     if (like) {
         check_matrix(like, "like");
-        if (!like->perm || !like->col_order_only || like->ncols != A->ncols) fail(GrB_INVALID_VALUE, "GrX_Matrix_shard_setup: `like` carries no column order of this width");
-        P = like->perm;
+        if (!like->order.perm || !like->order.col_order_only || like->ncols != A->ncols) fail(GrB_INVALID_VALUE, "GrX_Matrix_shard_setup: `like` carries no column order of this width");
+        P = like->order.perm;
         perm_retain(P);
     } else {
         if (!col_counts) fail(GrB_NULL_POINTER, "GrX_Matrix_shard_setup: col_counts is NULL");
@@ -2414,15 +2385,57 @@ extern "C" GrB_Info GrX_Matrix_shard_setup(GrB_Matrix A, const uint32_t *col_cou
         }
         sync_stream();
     }
-    if (A->ord) {
-        matrix_free(A->ord);
-        A->ord = nullptr;
+    if (A->order.ord) {
+        matrix_free(A->order.ord);
+        A->order.ord = nullptr;
     }
-    A->ord_state = 0;
-    perm_release(A->perm);
-    A->perm = P;
-    A->col_order_only = true;
+    A->order.ord_state = 0;
+    perm_release(A->order.perm);
+    A->order.perm = P;
+    A->order.col_order_only = true;
     GRB_CATCH(errp(A))
+}
+
+// ---- device bytes of the cached layouts: one term per group (the small tables -- class bounds, workgroup table, dictionary -- are not counted)
+uint64_t GB_Matrix_opaque::RowTiles::bytes(uint64_t vs, bool dict) const
+{
+    if (rt_state != 1) return 0;
+    return (uint64_t)rt_units * RT_EPL * (6 + (d_rt_val ? (dict && vs == 4 ? 1 : vs) : 0)) + 36ull * (uint64_t)rt_ntiles;
+}
+uint64_t GB_Matrix_opaque::TaggedGroups::bytes(uint64_t nrows, uint64_t vs, bool dict) const
+{
+    if (tg_state == 1) return (uint64_t)tg_units * TAG_EPL * (5 + (d_tg_val ? (dict ? 1 : vs) : 0)) + 12ull * ((nrows + 63) / 64);
+    if (tg_state == 2) return 12ull * ((nrows + 63) / 64);  // (offsets and non-empty words only: the entries are built when a call needs them)
+    return 0;
+}
+uint64_t GB_Matrix_opaque::Strips::hot_bytes() const
+{
+    const uint64_t hot_lanes = (uint64_t)strip_cb[strip_ncls + hub_ncls] * 64;
+    return hot_lanes * (uint64_t)hrec_bytes + (d_sslot16 ? hot_lanes * 2 + hot_lanes / 16 : hot_lanes * 4) + hot_lanes / 8;
+}
+uint64_t GB_Matrix_opaque::ColdTiles::bytes(uint64_t vs) const
+{
+    const uint64_t cold = (uint64_t)ct_units * CT_EPL;
+    return cold * ((d_ct_loc ? 6 : 4) + (d_ct_val ? (ct_mode == 2 ? 1 : vs) : 0)) + 20ull * (uint64_t)ct_ntiles;
+}
+uint64_t GB_Matrix_opaque::RowSplit::bytes(uint64_t nrows, uint64_t vs, bool dict) const
+{
+    if (split_state != 1) return 0;
+    const GB_Matrix_opaque *S = short_part.get();
+    uint64_t b = 8ull * (nrows + 1) + (short_tagged_only ? 0 : 4ull * (uint64_t)S->nvals + (S->iso ? vs : vs * (uint64_t)S->nvals));
+    b += bits_words64(nrows) * 8 + 4ull * (uint64_t)n_long + 4ull * bits_words64(nrows) + 16ull * (uint64_t)n_chunks;
+    if (d_probe) b += 4ull * (uint64_t)probe_k * (uint64_t)n_long;
+    b += rtile.bytes(vs, dict) + tagged.bytes(nrows, vs, dict);
+    if (split_kind == 4 && (strips.strip_nseg > 0 || cold.ct_units > 0)) {
+        b += strips.hot_bytes() + cold.bytes(vs);
+    } else if (split_kind == 2 && strips.strip_nseg > 0) {
+        const uint64_t padded = (uint64_t)strips.strip_cb[strips.strip_ncls] * STRIP_CH;
+        b += padded * 4 + (d_lval ? padded * vs : 0) + padded / 2 + padded / STRIP_CH * 8;
+    } else if (n_items > 0) {
+        const uint64_t padded = (uint64_t)long_nnz + 4ull * (uint64_t)n_items;
+        b += padded * 4 + (d_lval ? padded * vs : 0) + 16ull * (uint64_t)n_items;
+    }
+    return b;
 }
 
 extern "C" GrB_Info GrX_Matrix_cache_bytes(const GrB_Matrix A, uint64_t *bytes)
@@ -2431,34 +2444,11 @@ extern "C" GrB_Info GrX_Matrix_cache_bytes(const GrB_Matrix A, uint64_t *bytes)
     require_init();
     check_matrix(A, "A");
     if (!bytes) fail(GrB_NULL_POINTER, "bytes is NULL");
-    uint64_t b = 0;
-    const uint64_t vs = A->type->size;
-    if (A->d_tile_row) b += 8ull * (uint64_t)(A->n_tiles + 1);
-    if (A->d_col_hot) b += 4ull * (uint64_t)A->nvals;
-    if (A->d_hot_cols) b += 4ull * (uint64_t)A->hot_k;
-    if (A->split_state == 1) {
-        const GB_Matrix_opaque *S = A->short_part;
-        b += 8ull * (A->nrows + 1) + (A->short_tagged_only ? 0 : 4ull * (uint64_t)S->nvals + (S->iso ? vs : vs * (uint64_t)S->nvals));
-        b += bits_words64(A->nrows) * 8 + 4ull * (uint64_t)A->n_long + 4ull * bits_words64(A->nrows) + 16ull * (uint64_t)A->n_chunks;
-        if (A->d_probe) b += 4ull * (uint64_t)A->probe_k * (uint64_t)A->n_long;
-        if (A->rt_state == 1) b += (uint64_t)A->rt_units * RT_EPL * (6 + (A->d_rt_val ? (A->vdict_n > 0 && vs == 4 ? 1 : vs) : 0)) + 36ull * (uint64_t)A->rt_ntiles;
-        if (A->tg_state == 1) b += (uint64_t)A->tg_units * TAG_EPL * (5 + (A->d_tg_val ? (A->vdict_n > 0 ? 1 : vs) : 0)) + 12ull * ((A->nrows + 63) / 64);
-        else if (A->tg_state == 2) b += 12ull * ((A->nrows + 63) / 64);  // (offsets and non-empty words only: the entries are built when a call needs them)
-        if (A->split_kind == 4 && (A->strip_nseg > 0 || A->ct_units > 0)) {
-            const uint64_t hot_lanes = (uint64_t)A->strip_cb[A->strip_ncls + A->hub_ncls] * 64;
-            const uint64_t cold = (uint64_t)A->ct_units * CT_EPL;
-            b += hot_lanes * (uint64_t)A->hrec_bytes + (A->d_sslot16 ? hot_lanes * 2 + hot_lanes / 16 : hot_lanes * 4) + hot_lanes / 8 + cold * ((A->d_ct_loc ? 6 : 4) + (A->d_ct_val ? (A->ct_mode == 2 ? 1 : vs) : 0)) + 20ull * (uint64_t)A->ct_ntiles;
-        } else if (A->split_kind == 2 && A->strip_nseg > 0) {
-            const uint64_t padded = (uint64_t)A->strip_cb[A->strip_ncls] * STRIP_CH;
-            b += padded * 4 + (A->d_lval ? padded * vs : 0) + padded / 2 + padded / STRIP_CH * 8;
-        } else if (A->n_items > 0) {
-            const uint64_t padded = (uint64_t)A->long_nnz + 4ull * (uint64_t)A->n_items;
-            b += padded * 4 + (A->d_lval ? padded * vs : 0) + 16ull * (uint64_t)A->n_items;
-        }
-    }
-    if (A->ord) {  // the popularity-ordered twin: its layouts, its row pointers, the two maps of the order
+    uint64_t b = A->tile.bytes() + A->hot.bytes() + A->split.bytes(A->nrows, A->type->size, A->vd.vdict_n > 0);
+    if (A->col_hot()) b += 4ull * (uint64_t)A->nvals;  // (the re-coded columns; an ordered twin's own column array while it has one)
+    if (A->order.ord) {  // the popularity-ordered twin: its layouts, its row pointers, the two maps of the order
         uint64_t tb = 0;
-        (void)GrX_Matrix_cache_bytes(A->ord, &tb);
+        (void)GrX_Matrix_cache_bytes(A->order.ord, &tb);
         b += tb + 8ull * (A->nrows + 1) + 8ull * A->nrows;
     }
     *bytes = b;

@@ -647,131 +647,27 @@ int64_t vector_index_list(GB_Vector_opaque *v, uint64_t **d_idx)
 // ---------------------------------------------------------------------------------------------------
 GB_Matrix_opaque *matrix_new(GrB_Type type, uint64_t nrows, uint64_t ncols)
 {
-    auto *A = new GB_Matrix_opaque();
+    auto *A = new GB_Matrix_opaque();  // (everything else starts from its default member initialiser)
     A->magic = MAGIC_MATRIX;
     A->type = type;
     A->nrows = nrows;
     A->ncols = ncols;
-    A->nvals = 0;
-    A->d_ptr = nullptr;
-    A->d_col = nullptr;
-    A->d_val = nullptr;
-    A->iso = false;
-    A->owns = true;
-    A->tr = nullptr;
-    A->d_tile_row = nullptr;
-    A->n_tiles = 0;
-    A->tile_items = 0;
-    A->d_col_hot = nullptr;
-    A->d_hot_cols = nullptr;
-    A->hot_k = 0;
-    A->hot_state = 0;
-    A->hot_cols_dropped = false;
-    A->short_part = nullptr;
-    A->d_long_bits = nullptr;
-    A->d_long_rows = nullptr;
-    A->d_chunk_slot = nullptr;
-    A->d_chunk_start = nullptr;
-    A->d_chunk_len = nullptr;
-    A->d_long_prefix = nullptr;
-    A->d_lcol = nullptr;
-    A->d_lval = nullptr;
-    A->d_it_start = nullptr;
-    A->d_it_len = nullptr;
-    A->d_it_slot = nullptr;
-    A->d_item_begin = nullptr;
-    A->long_nnz = 0;
-    A->n_items = 0;
-    for (auto &x : A->item_begin) x = 0;
-    A->n_long = A->n_chunks = 0;
-    A->split_state = 0;
-    A->split_hot = false;
     return A;
 }
 
+// Drops everything the products cache with A; what describes A (its arrays, `ranked`, `tr_of`, `hot_identity`) stays.
 void matrix_invalidate_caches(GB_Matrix_opaque *A)
 {
-    if (A->tr) {
-        matrix_free(A->tr);
-        A->tr = nullptr;
-    }
-    if (A->ord) {
-        matrix_free(A->ord);
-        A->ord = nullptr;
-    }
-    perm_release(A->perm);  // (vectors in this order keep it alive until they are converted)
-    A->perm = nullptr;
-    A->col_order_only = false;  // (a shard set-up describes the content that is going away)
-    A->ord_state = 0;
-    dev_free(A->d_cold_bounds); dev_free(A->d_ct_order);
-    A->d_cold_bounds = nullptr; A->d_ct_order = nullptr; A->ct_ntiles = 0;
-    if (A->hot_identity) A->d_col_hot = nullptr;  // (an alias of d_col)
-    dev_free(A->d_tile_row);
-    A->d_tile_row = nullptr;
-    A->n_tiles = 0;
-    A->tile_items = 0;
-    dev_free(A->d_col_hot);
-    dev_free(A->d_hot_cols);
-    A->d_col_hot = nullptr;
-    A->d_hot_cols = nullptr;
-    A->hot_k = 0;
-    A->hot_state = 0;
-    A->hot_cols_dropped = false;
-    if (A->short_part) matrix_free(A->short_part);
-    A->short_part = nullptr;
-    dev_free(A->d_long_bits);
-    dev_free(A->d_long_rows);
-    dev_free(A->d_chunk_slot);
-    dev_free(A->d_chunk_start);
-    dev_free(A->d_chunk_len);
-    dev_free(A->d_long_prefix);
-    dev_free(A->d_lcol);
-    dev_free(A->d_lval);
-    dev_free(A->d_it_start);
-    dev_free(A->d_it_len);
-    dev_free(A->d_it_slot);
-    dev_free(A->d_item_begin);
-    dev_free(A->d_sstart);
-    dev_free(A->d_sslot);
-    dev_free(A->d_sslot16); dev_free(A->d_sslot_base);
-    A->d_sslot16 = nullptr; A->d_sslot_base = nullptr;
-    dev_free(A->d_hrec);
-    dev_free(A->d_vdict); dev_free(A->d_vd_table); dev_free(A->d_vd_codes);
-    A->d_vdict = nullptr; A->d_vd_table = nullptr; A->d_vd_codes = nullptr;
-    A->vdict_n = 0;
-    dev_free(A->d_ct_col); dev_free(A->d_ct_val); dev_free(A->d_ct_loc); dev_free(A->d_ct_tiles);
-    A->d_ct_col = nullptr; A->d_ct_val = nullptr; A->d_ct_loc = nullptr; A->d_ct_tiles = nullptr; A->ct_units = 0;
-    A->d_sstart = nullptr;
-    A->d_sslot = nullptr;
-    A->d_hrec = nullptr;
-    A->strip_nseg = 0;
-    A->hub_ncls = 0;
-    dev_free(A->d_wg_tab); dev_free(A->d_strip_cb);
-    A->d_wg_tab = nullptr; A->d_strip_cb = nullptr; A->wg_tab_g = 0;
+    matrix_free(A->tr);
+    A->tr = nullptr;
+    matrix_free(A->order.ord);
+    perm_release(A->order.perm);  // (vectors in this order keep it alive until they are converted)
+    A->order = {};                // (with col_order_only: a shard set-up describes the content that is going away)
+    A->tile = {};
+    A->hot = {};
+    A->vd = {};
+    A->split = {};
     A->pull_calls = 0;
-    dev_free(A->d_tg_off); dev_free(A->d_tg_col); dev_free(A->d_tg_val); dev_free(A->d_tg_tag); dev_free(A->d_tg_nonempty);
-    A->d_tg_off = nullptr; A->d_tg_col = nullptr; A->d_tg_val = nullptr; A->d_tg_tag = nullptr; A->d_tg_nonempty = nullptr;
-    dev_free(A->d_probe); A->d_probe = nullptr; A->probe_k = 0;
-    dev_free(A->d_rt_col); dev_free(A->d_rt_tag); dev_free(A->d_rt_val); dev_free(A->d_rt_tiles); dev_free(A->d_rt_order); dev_free(A->d_rt_counter);
-    A->d_rt_col = nullptr; A->d_rt_tag = nullptr; A->d_rt_val = nullptr; A->d_rt_tiles = nullptr; A->d_rt_order = nullptr; A->d_rt_counter = nullptr;
-    A->rt_state = 0; A->rt_units = 0; A->rt_ntiles = 0;
-    A->tg_state = 0;
-    A->d_lcol = nullptr;
-    A->d_lval = nullptr;
-    A->d_it_start = nullptr;
-    A->d_it_len = nullptr;
-    A->d_it_slot = nullptr;
-    A->d_item_begin = nullptr;
-    A->long_nnz = 0;
-    A->n_items = 0;
-    A->d_long_bits = nullptr;
-    A->d_long_rows = nullptr;
-    A->d_chunk_slot = nullptr;
-    A->d_chunk_start = nullptr;
-    A->d_chunk_len = nullptr;
-    A->d_long_prefix = nullptr;
-    A->n_long = A->n_chunks = 0;
-    A->split_state = 0;
 }
 
 void matrix_release_storage(GB_Matrix_opaque *A)

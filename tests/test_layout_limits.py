@@ -596,3 +596,108 @@ def test_last_resident_code_of_a_class_head(dev, tname):
                 assert (got > base) if more else (got < base), (level, move, got, base)
     finally:
         reset_opts()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# 6. the lifetime of the cached layouts: built, extended, rebuilt, dropped, built again
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _lifecycle_matrix():
+    """300 rows, 2048 columns, FP32 values from 1 .. 200 (a dictionary is built).  Rows 0 .. 23 are long: 96 entries each, 48 on the
+    resident codes below hot_k = 256 (hot strips) and 48 behind them (cold tiles) -- 2304 entries, more than 30 % of all, so the split
+    is built.  The other rows hold 0 .. 3 entries anywhere (the short part: tagged row groups and sorted row tiles)."""
+    m, n = 300, 2048
+    rows_l, cols_l = [], []
+    for r in range(24):
+        cc = np.concatenate([(np.arange(48) * 5 + r) % 256, 256 + (np.arange(48) * 37 + r * 3) % (n - 256)])
+        rows_l.append(np.full(cc.size, r)); cols_l.append(cc)
+    i = np.arange(24, m)
+    cnt = np.array([0, 1, 2, 3, 1])[i % 5]
+    rr = np.repeat(i, cnt)
+    first = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    kth = np.arange(rr.size) - np.repeat(first, cnt)
+    rows_l.append(rr); cols_l.append((rr * 29 + kth * 683) % n)
+    rows, cols = np.concatenate(rows_l).astype(np.int64), np.concatenate(cols_l).astype(np.int64)
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    assert (np.diff(rows * n + cols) > 0).all()
+    vals = (1 + (rows * 7 + cols * 3) % 200).astype(np.float32)
+    return rows, cols, vals, m, n
+
+
+def test_layouts_are_built_extended_rebuilt_dropped_and_built_again(gb):
+    """Every cached layout of one matrix through its whole life, with GrX_Matrix_cache_bytes as the witness that what was dropped was
+    released and what was rebuilt is what was there before -- a layout that one of the steps forgets to drop, or keeps half of, shows as
+    a byte count that does not return.  The matrix (see _lifecycle_matrix) carries the ranked hint and gets the ordered twin with a value
+    dictionary, hot strips, cold tiles, the index of the tagged row groups and sorted row tiles.  Every product is compared with the
+    oracle element for element (small integer values: exact).
+
+    1. three min_plus products of a full operand: the layouts are built at the first; the bytes are recorded;
+    2. a plus_times product of a sparse operand, which the row tiles do not take: the ENTRIES of the tagged row groups are built now, from
+       the tiles (lazy_tagged) -- the bytes grow by exactly those: 4 (column) + 1 (row tag) + 1 (value code) bytes per entry, the entries of
+       every group of 64 rows padded to a multiple of 4;
+    3. long_classes 16 -> 32 and back: each change rebuilds the twin and its split; after the way back the bytes are those of step 2;
+    4. ONE value is changed in place, which drops every cached layout: 0 bytes; three products against the oracle; the bytes of step 1.
+       (GrB_Matrix_setElement is not implemented by this library; the in-place element-wise update A = A (+) D with `second` and a D
+       of one entry sets that one value and invalidates the caches like any other write to A.)"""
+    from graphblas_amd import device
+
+    rows, cols, vals, m, n = _lifecycle_matrix()
+    tname = "FP32"
+    oa = O.OMat.from_coo(rows, cols, vals, m, n, tname)
+    fi, fv = _operand(n, tname)
+    si = np.unique(np.concatenate([np.arange(0, n, 3), np.arange(1, 256, 7)]))
+    sv = (1 + si % 9).astype(np.float32)
+    full, ofull = gb.Vector.from_coo(fi, fv, dtype=tname, size=n), O.OVec(n, fi, fv, tname)
+    sparse, osparse = gb.Vector.from_coo(si, sv, dtype=tname, size=n), O.OVec(n, si, sv, tname)
+    # (the short part: the rows with fewer than split_min_len = 8 entries)
+    deg = np.bincount(rows, minlength=m)
+    short = np.where(deg < 8, deg, 0)
+    per_group = np.add.reduceat(short, np.arange(0, m, 64))
+    tagged_entry_bytes = int(((per_group + 3) // 4).sum()) * 4 * 6
+
+    def full_products(oa, where):
+        exp = O.mxv(oa, ofull, "min_plus")
+        for call in range(3):
+            same_vec(A.mxv(full, gb.semiring.min_plus).new(), exp, where=f"{where}, full operand, call {call}")
+            st = device.last_stats()
+            assert st["ordered"] == 1 and st["long_kernel"] == 4 and st["fused_epilogue"] == 3 and st["value_dict"] > 0, (where, call, st)
+
+    def sparse_product(oa, where):
+        same_vec(A.mxv(sparse, gb.semiring.plus_times).new(), O.mxv(oa, osparse, "plus_times"), where=f"{where}, sparse operand")
+        st = device.last_stats()
+        assert st["ordered"] == 1 and st["fused_epilogue"] == 1, (where, st)
+
+    opts = ORDER_OPTS + ((b"hot_k", 256), (b"hub_min_len", 0), (b"long_classes", 16), (b"lazy_tagged", 1))
+    try:
+        set_opts(opts)
+        A = _build(gb, rows, cols, vals, m, n, tname)
+        assert device.matrix_cache_bytes(A) == 0
+        # 1
+        full_products(oa, "step 1")
+        built = device.matrix_cache_bytes(A)
+        assert built > 0
+        # 2
+        sparse_product(oa, "step 2")
+        extended = device.matrix_cache_bytes(A)
+        assert extended - built == tagged_entry_bytes, (built, extended, tagged_entry_bytes)
+        # 3
+        set_opts(((b"long_classes", 32),))
+        full_products(oa, "step 3, 32 classes")
+        sparse_product(oa, "step 3, 32 classes")
+        set_opts(((b"long_classes", 16),))
+        full_products(oa, "step 3, 16 classes again")
+        sparse_product(oa, "step 3, 16 classes again")
+        assert device.matrix_cache_bytes(A) == extended, (device.matrix_cache_bytes(A), extended)
+        # 4
+        k = int(np.flatnonzero(rows == 5)[50])  # (a cold entry of a long row)
+        new_val = np.float32(7 if vals[k] != 7 else 8)
+        D = gb.Matrix.from_coo(rows[k : k + 1], cols[k : k + 1], np.array([new_val], np.float32), dtype=tname, nrows=m, ncols=n)
+        A << A.ewise_add(D, gb.binary.second)
+        assert device.matrix_cache_bytes(A) == 0
+        vals2 = vals.copy()
+        vals2[k] = new_val
+        oa2 = O.OMat.from_coo(rows, cols, vals2, m, n, tname)
+        full_products(oa2, "step 4")
+        assert device.matrix_cache_bytes(A) == built, (device.matrix_cache_bytes(A), built)
+    finally:
+        reset_opts()
