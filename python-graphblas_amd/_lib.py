@@ -116,6 +116,7 @@ def _declare(L):
                   ("UINT64", ctypes.c_uint64), ("FP32", ctypes.c_float), ("FP64", ctypes.c_double)):
         getattr(L, f"GrB_Vector_setElement_{t}").argtypes = [c_void_p, ct, c_u64]
         getattr(L, f"GrB_Vector_extractElement_{t}").argtypes = [P(ct), c_void_p, c_u64]
+        getattr(L, f"GrB_Matrix_extractElement_{t}").argtypes = [P(ct), c_void_p, c_u64, c_u64]
         getattr(L, f"GrB_Vector_assign_{t}").argtypes = [c_void_p, c_void_p, c_void_p, ct, c_void_p, c_u64, c_void_p]
         getattr(L, f"GrB_Vector_reduce_{t}").argtypes = [P(ct), c_void_p, c_void_p, c_void_p, c_void_p]
         getattr(L, f"GrB_Scalar_setElement_{t}").argtypes = [c_void_p, ct]
@@ -149,6 +150,10 @@ def _declare(L):
     L.GrX_get_stream.argtypes = [P(c_void_p)]
     L.GrB_Vector_assign.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]
     L.GrB_Vector_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]
+    # (C, Mask, accum, A, I, ni, J, nj, desc) / (w, mask, accum, A, I, ni, j, desc)
+    L.GrB_Matrix_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
+    L.GrB_Col_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p]
+    L.GrB_Matrix_extractElement_Scalar.argtypes = [c_void_p, c_void_p, c_u64, c_u64]
     L.GrX_option_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
     L.GrX_option_get.argtypes = [ctypes.c_char_p, P(ctypes.c_int64)]
     L.GrX_options_reset.argtypes = []

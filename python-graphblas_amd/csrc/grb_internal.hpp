@@ -202,6 +202,7 @@ void preload_vecops();
 void preload_object();
 void preload_prim();
 void preload_select();
+void preload_extract();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)

@@ -219,6 +219,39 @@ extern "C" GrB_Info GrB_Vector_extractElement_Scalar(GrB_Scalar s, const GrB_Vec
     return rc;
     GRB_CATCH(errp(s))
 }
+extern "C" GrB_Info GrB_Matrix_extractElement_Scalar(GrB_Scalar s, const GrB_Matrix A, GrB_Index i, GrB_Index j)
+{
+    GRB_TRY
+    check_scalar(s, "s");
+    check_matrix(A, "A");
+    // (as the vector form: read through the widest exact type of A's kind, store in the scalar's own type)
+    GrB_Info rc;
+    const int tc = A->type->code;
+    if (tc == TC_FP32 || tc == TC_FP64) {
+        double v = 0;
+        rc = GrB_Matrix_extractElement_FP64(&v, A, i, j);
+        if (rc == GrB_SUCCESS) scalar_set<double>(s, v);
+    } else if (tc == TC_UINT64) {
+        uint64_t v = 0;
+        rc = GrB_Matrix_extractElement_UINT64(&v, A, i, j);
+        if (rc == GrB_SUCCESS) scalar_set<uint64_t>(s, v);
+    } else {
+        int64_t v = 0;
+        rc = GrB_Matrix_extractElement_INT64(&v, A, i, j);
+        if (rc == GrB_SUCCESS) scalar_set<int64_t>(s, v);
+    }
+    if (rc == GrB_NO_VALUE) {
+        s->has = false;
+        rc = GrB_SUCCESS;  // (C API 2.0: an absent element empties the scalar)
+    }
+    if (rc != GrB_SUCCESS) {  // (the typed entry point left its text on A)
+        const char *msg = nullptr;
+        GrB_Matrix_error(&msg, A);
+        s->err = msg ? msg : "";
+    }
+    return rc;
+    GRB_CATCH(errp(s))
+}
 extern "C" GrB_Info GrB_Vector_assign_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Scalar s,
                                              const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc)
 {
@@ -264,8 +297,6 @@ NI_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)
 NI_M(GrB_Matrix_assign, const GrB_Matrix, const GrB_BinaryOp, const GrB_Matrix, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
 NI_M(GrB_Row_assign, const GrB_Vector, const GrB_BinaryOp, const GrB_Vector, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
 NI_M(GrB_Col_assign, const GrB_Vector, const GrB_BinaryOp, const GrB_Vector, const GrB_Index *, GrB_Index, GrB_Index, const GrB_Descriptor)
-NI_M(GrB_Matrix_extract, const GrB_Matrix, const GrB_BinaryOp, const GrB_Matrix, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
-NI_V(GrB_Col_extract, const GrB_Vector, const GrB_BinaryOp, const GrB_Matrix, const GrB_Index *, GrB_Index, GrB_Index, const GrB_Descriptor)
 NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Descriptor)
 NI_M(GrB_Matrix_removeElement, GrB_Index, GrB_Index)
 NI_M(GrB_Matrix_assign_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_Scalar, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
@@ -279,7 +310,6 @@ NI_M(GrB_Matrix_apply_IndexOp_Scalar, const GrB_Matrix, const GrB_BinaryOp, cons
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Vector, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
-extern "C" GrB_Info GrB_Matrix_extractElement_Scalar(GrB_Scalar, const GrB_Matrix, GrB_Index, GrB_Index) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Matrix_diag(GrB_Matrix *, const GrB_Vector, int64_t) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Type_new(GrB_Type *, size_t) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_UnaryOp_new(GrB_UnaryOp *, void *, GrB_Type, GrB_Type) { return GrB_NOT_IMPLEMENTED; }
@@ -304,7 +334,6 @@ extern "C" GrB_Info GrB_Semiring_new(GrB_Semiring *, GrB_Monoid, GrB_BinaryOp) {
     }                                                                                                                                \
     extern "C" GrB_Info GrB_Monoid_new_##NAME(GrB_Monoid *, GrB_BinaryOp, ctype) { return GrB_NOT_IMPLEMENTED; }                     \
     NI_M(GrB_Matrix_setElement_##NAME, ctype, GrB_Index, GrB_Index)                                                                  \
-    extern "C" GrB_Info GrB_Matrix_extractElement_##NAME(ctype *, const GrB_Matrix, GrB_Index, GrB_Index) { return GrB_NOT_IMPLEMENTED; } \
     extern "C" GrB_Info GrB_Matrix_reduce_##NAME(ctype *, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; } \
     NI_M(GrB_Matrix_assign_##NAME, const GrB_Matrix, const GrB_BinaryOp, ctype, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor) \
     NI_V(GrB_Vector_apply_BinaryOp1st_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, ctype, const GrB_Vector, const GrB_Descriptor) \

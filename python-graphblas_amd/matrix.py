@@ -1,7 +1,7 @@
 """Matrix / TransposedMatrix: the host-side mirror of graphblas/core/matrix.py for the path --
 constructor :190-203, ``__del__`` :218-225, ``build`` :627-681, ``from_coo`` :818-894, ``_from_csx``
 :992-1068, ``to_coo`` :525-594, ``_to_csx`` :1601-1645, ``isequal`` :373-415, ``ewise_add`` :1861-1950,
-``ewise_mult`` :1952-2041, ``mxv`` :2203-2262, ``mxm`` :2264-2331, ``TransposedMatrix`` :3900-3960."""
+``ewise_mult`` :1952-2041, ``mxv`` :2203-2262, ``mxm`` :2264-2331, ``__getitem__`` :3020-3090, ``TransposedMatrix`` :3900-3960."""
 from __future__ import annotations
 
 import ctypes
@@ -9,11 +9,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .base import BaseType, Expression, InfixMatMul, call, call_on, select_expression
+from .base import BaseType, Expression, InfixMatMul, Mask, ScalarExpression, call, call_on, select_expression
 from .dtypes import lookup_dtype
 from .exceptions import DimensionMismatch
 from .operators import binary as _binary, get_typed_op, monoid as _monoid, semiring as _semiring
-from .vector import Vector, _name_counter, _ptr
+from .vector import Vector, _iptr, _name_counter, _ptr
 
 GrB_CSR_FORMAT, GrB_CSC_FORMAT = 0, 1
 
@@ -350,6 +350,11 @@ class Matrix(BaseType):
         mask) keeps (reference core/matrix.py:2597-2623 -> C ``GrB_Matrix_select_<T>``)."""
         return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape)
 
+    def __getitem__(self, keys):
+        """``A[I, J]`` -> matrix expression, ``A[i, J]`` / ``A[I, j]`` -> vector expression, ``A[i, j]`` -> scalar expression
+        (reference core/matrix.py:3020-3090 -> ``GrB_Matrix_extract`` / ``GrB_Col_extract`` / ``GrB_Matrix_extractElement_<T>``)."""
+        return _extract(self, keys)
+
     def __matmul__(self, other):
         return InfixMatMul(self, other)
 
@@ -406,6 +411,10 @@ class TransposedMatrix:
         """``A.T.select(op, thunk)``: the selection runs on the transpose (descriptor T0)."""
         return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape, at=True)
 
+    def __getitem__(self, keys):
+        """``A.T[I, J]``: the same expressions with the roles of rows and columns swapped (descriptor T0)."""
+        return _extract(self, keys)
+
     def __matmul__(self, other):
         return InfixMatMul(self, other)
 
@@ -413,6 +422,89 @@ class TransposedMatrix:
         C = Matrix(dtype or self.dtype, self._nrows, self._ncols, name=name)
         call("GrB_transpose", [C, None, None, self._matrix, None])
         return C
+
+
+class _AxisIndex:
+    """One index of ``A[., .]`` resolved against its dimension (reference core/expr.py:176-251, IndexerResolver.parse_index): an int is
+    a scalar index; a full ``:`` is ``GrB_ALL``; any other slice is ``np.arange``; a list or a 1-D integer array is taken as it is
+    (negative entries count from the end).  Anything else is a ``TypeError``; indices beyond the dimension are the library's
+    ``GrB_INDEX_OUT_OF_BOUNDS``."""
+
+    def __init__(self, key, size):
+        self.scalar = self.array = None
+        self.size = size  # how many indices the axis selects (scalar: None)
+        if isinstance(key, (int, np.integer)) and not isinstance(key, (bool, np.bool_)):
+            i = int(key)
+            if i >= size or i < -size:
+                raise IndexError(f"Index out of range: index={i}, size={size}")
+            self.scalar, self.size = i + size if i < 0 else i, None
+        elif isinstance(key, slice):
+            if key != slice(None):
+                self.array = np.arange(*key.indices(size), dtype=np.uint64)
+                self.size = int(self.array.size)
+        elif isinstance(key, np.ndarray) or type(key) is list:
+            a = key if isinstance(key, np.ndarray) else (np.asarray(key) if len(key) else np.zeros(0, np.uint64))
+            if a.ndim != 1:
+                raise TypeError(f"Invalid number of dimensions for index: {a.ndim}")
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"Invalid dtype for index: {a.dtype}")
+            if a.dtype.kind == "i" and a.size and a.min() < 0:
+                a = np.where(a < 0, a + size, a)
+                if a.min() < 0:
+                    raise IndexError(f"Index out of range: index={int(a.min()) - size}, size={size}")
+            self.array = np.ascontiguousarray(a, dtype=np.uint64)
+            self.size = int(self.array.size)
+        elif isinstance(key, (Mask, BaseType, TransposedMatrix)):
+            raise TypeError(f"Invalid type for index: {type(key).__name__}.\nIf you want to apply a mask, perhaps do something like `x.dup(mask=M.S)`.")
+        else:
+            raise TypeError(f"Invalid type for index: {type(key).__name__}; integers, slices, lists and 1-D integer arrays are supported")
+
+    @property
+    def cargs(self):
+        """(pointer, count) as the C entry points take an index list"""
+        if self.array is None:
+            return _lib.all_indices(), ctypes.c_uint64(self.size)
+        return _iptr(self.array), ctypes.c_uint64(self.size)
+
+
+class _MatrixElementExpr(ScalarExpression):
+    """``A[i, j]``: read with ``.new()`` / ``.value`` / a comparison (reference core/matrix.py:3020-3050)."""
+
+    def __init__(self, matrix, row, col):
+        self.parent, self.row, self.col = matrix, row, col
+        super().__init__(self._read, matrix.dtype)
+
+    def _read(self):
+        A = self.parent
+        out = np.ctypeslib.as_ctypes_type(A.dtype.np_type)()
+        info = getattr(_lib.lib, f"GrB_Matrix_extractElement_{A.dtype.name}")(ctypes.byref(out), A._handle, self.row, self.col)
+        if info == _lib.GrB_NO_VALUE:
+            return None
+        from .exceptions import check_status
+
+        check_status(info, A)
+        return A.dtype.np_type.type(out.value).item()
+
+
+def _extract(A, keys):
+    if not isinstance(keys, tuple) or len(keys) != 2:
+        raise TypeError(f"Invalid index for a Matrix: a pair `A[rows, columns]` is required; got {keys!r}")
+    base, at = A._matrix, A._is_transposed
+    rows, cols = _AxisIndex(keys[0], A._nrows), _AxisIndex(keys[1], A._ncols)
+    if rows.scalar is not None and cols.scalar is not None:
+        i, j = (cols.scalar, rows.scalar) if at else (rows.scalar, cols.scalar)
+        return _MatrixElementExpr(base, i, j)
+    if rows.scalar is None and cols.scalar is None:
+        expr = Expression("extract", "GrB_Matrix_extract", [base, *rows.cargs, *cols.cargs], op=None, output_type=Matrix,
+                          shape=(rows.size, cols.size), at=at, dtype=base.dtype)
+    else:
+        # A[i, J] is the reference's spelling of GrB_Col_extract with T0 (row i of A); on A.T the roles swap
+        row_form = rows.scalar is not None
+        lst, j = (cols, rows.scalar) if row_form else (rows, cols.scalar)
+        expr = Expression("extract", "GrB_Col_extract", [base, *lst.cargs, ctypes.c_uint64(j)], op=None, output_type=Vector,
+                          shape=(lst.size,), at=row_form != at, dtype=base.dtype)
+    expr._index_arrays = (rows.array, cols.array)  # (the C call reads them: kept alive with the expression)
+    return expr
 
 
 def _reduce_vector(A, op, method_name, transpose):
