@@ -27,20 +27,6 @@ namespace grb {
 
 constexpr int EXT_UNIT = 8192;  // entries of a unit
 
-static dim3 ext_grid(int64_t threads) { return dim3((unsigned)std::max<int64_t>(1, ceil_div(threads, 256))); }
-
-// first p in [lo, hi) with a[p] >= key (hi if none): a sorted ascending
-template <typename K>
-__device__ __forceinline__ int64_t ext_lower_bound(const K *__restrict__ a, int64_t lo, int64_t hi, K key)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // an index of a list at or beyond the dimension it indexes raises the flag
 __global__ void k_ext_check(const uint64_t *__restrict__ L, int64_t n, uint64_t dim, int *oob)
 {
@@ -63,8 +49,8 @@ __global__ void k_ext_rowseg(const int64_t *__restrict__ Sp, const int32_t *__re
             a = Sp[r];
             b = Sp[r + 1];
             if constexpr (NARROW) {
-                a = ext_lower_bound<int32_t>(Sj, a, b, (int32_t)clo);
-                b = chi > INT32_MAX ? b : ext_lower_bound<int32_t>(Sj, a, b, (int32_t)chi);
+                a = lower_bound<int32_t>(Sj, a, b, (int32_t)clo);
+                b = chi > INT32_MAX ? b : lower_bound<int32_t>(Sj, a, b, (int32_t)chi);
             }
         }
         seg[i] = a;
@@ -141,7 +127,7 @@ __global__ void __launch_bounds__(256) k_ext_pick(const int32_t *__restrict__ Sj
             const int32_t col = Sj[w.src + k];
             if constexpr (TABLE) jn = jinv[col];
             else {
-                const int64_t p = ext_lower_bound<uint64_t>(J, 0, nj, (uint64_t)col);
+                const int64_t p = lower_bound<uint64_t>(J, 0, nj, (uint64_t)col);
                 if (p < nj && J[p] == (uint64_t)col) jn = (int32_t)p;
             }
         }
@@ -194,8 +180,8 @@ __global__ void __launch_bounds__(256) k_ext_dup(const int32_t *__restrict__ Sj,
         int64_t lb = 0, mult = 0;
         if (k < w.n) {
             const uint64_t col = (uint64_t)Sj[w.src + k];
-            lb = ext_lower_bound<uint64_t>(sJ, 0, nj, col);
-            mult = ext_lower_bound<uint64_t>(sJ, lb, nj, col + 1) - lb;
+            lb = lower_bound<uint64_t>(sJ, 0, nj, col);
+            mult = lower_bound<uint64_t>(sJ, lb, nj, col + 1) - lb;
         }
         int64_t incl = mult;  // inclusive sum over the lanes
         for (int d = 1; d < 64; d <<= 1) {
@@ -237,13 +223,6 @@ __global__ void k_ext_gather(const uint64_t *__restrict__ key, const uint32_t *_
     if (Tx) Tx[q] = Vx[pay[q]];
 }
 
-template <typename U>
-__global__ void k_ext_bcast(U *out, int64_t n, const U *src)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = src[0];
-}
-
 // ---- column / row / element -----------------------------------------------------------------------------------------------------------
 // t(k) = S(I[k], j), or with ROW  t(k) = S(j, I[k]): one search in a sorted row per k (I == nullptr: k itself)
 template <typename U>
@@ -258,7 +237,7 @@ __global__ void k_ext_col(const int64_t *__restrict__ Sp, const int32_t *__restr
         else {
             const int64_t row = row_form ? j : (int64_t)idx;
             const int32_t col = (int32_t)(row_form ? (int64_t)idx : j);
-            const int64_t e = Sp[row + 1], p = ext_lower_bound<int32_t>(Sj, Sp[row], e, col);
+            const int64_t e = Sp[row + 1], p = lower_bound<int32_t>(Sj, Sp[row], e, col);
             if (p < e && Sj[p] == col) {
                 has = true;
                 t_val[k] = Sx[a_iso ? 0 : p];
@@ -309,14 +288,6 @@ __global__ void __launch_bounds__(64) k_ext_element(const int64_t *__restrict__ 
     }
 }
 
-#define EXT_BY_SIZE(size, ...)                              \
-    switch (size) {                                         \
-    case 1: { using U = uint8_t; __VA_ARGS__; } break;      \
-    case 2: { using U = uint16_t; __VA_ARGS__; } break;     \
-    case 4: { using U = uint32_t; __VA_ARGS__; } break;     \
-    default: { using U = uint64_t; __VA_ARGS__; } break;    \
-    }
-
 static void ext_check_flag(int *d_flag, const char *what)
 {
     int h = 0;
@@ -326,7 +297,7 @@ static void ext_check_flag(int *d_flag, const char *what)
 
 // T (of type `ctype`, fresh storage, ni x nj) = S(I, J).  I / J == nullptr: GrB_ALL.  full_values: one value per entry even when S is iso
 // (the write rule reads one value per entry when it masks or accumulates)
-static GB_Matrix_opaque *extract_build(GB_Matrix_opaque *S, const uint64_t *I, uint64_t ni, const uint64_t *J, uint64_t nj, int ctype, bool full_values)
+static MatrixOwner extract_build(GB_Matrix_opaque *S, const uint64_t *I, uint64_t ni, const uint64_t *J, uint64_t nj, int ctype, bool full_values)
 {
     const int64_t m = (int64_t)S->nrows, n = (int64_t)S->ncols;
     if (!I) ni = (uint64_t)m;
@@ -350,180 +321,152 @@ static GB_Matrix_opaque *extract_build(GB_Matrix_opaque *S, const uint64_t *I, u
         DevBuf<int> oob(1, true);
         if (I && ni) {
             h2d(dI.p, I, sizeof(uint64_t) * (size_t)ni);
-            hipLaunchKernelGGL(k_ext_check, ext_grid((int64_t)ni), dim3(256), 0, ctx().stream, (const uint64_t *)dI.p, (int64_t)ni, (uint64_t)m, oob.p);
+            hipLaunchKernelGGL(k_ext_check, grid1d((int64_t)ni), dim3(256), 0, ctx().stream, (const uint64_t *)dI.p, (int64_t)ni, (uint64_t)m, oob.p);
             ctx().stats.kernel_launches += 1;
         }
         if (J && nj) {
             h2d(dJ.p, J, sizeof(uint64_t) * (size_t)nj);
-            hipLaunchKernelGGL(k_ext_check, ext_grid((int64_t)nj), dim3(256), 0, ctx().stream, (const uint64_t *)dJ.p, (int64_t)nj, (uint64_t)n, oob.p);
+            hipLaunchKernelGGL(k_ext_check, grid1d((int64_t)nj), dim3(256), 0, ctx().stream, (const uint64_t *)dJ.p, (int64_t)nj, (uint64_t)n, oob.p);
             ctx().stats.kernel_launches += 1;
         }
         ext_check_flag(oob.p, "GrB_Matrix_extract");
     }
     const int stype = S->type->code;
-    const size_t ssize = S->type->size, csize = type_size(ctype);
+    const size_t ssize = S->type->size;
     const bool t_iso = S->iso && !full_values;
     const int a_iso = S->iso ? 1 : 0;
     // ---- short cuts
     if (ni == 0 || nj == 0 || S->nvals == 0) {
         ctx().stats.method = 6;
-        return matrix_new(type_of_code(ctype), ni, nj);
+        return MatrixOwner(matrix_new(type_of_code(ctype), ni, nj));
     }
     if (!I && !J) {
         ctx().stats.method = 6;
-        GB_Matrix_opaque *Tm = matrix_cast_copy(S, ctype);
-        if (Tm->iso && full_values) {
-            try {
-                void *full = dev_alloc(csize * (size_t)Tm->nvals);
-                EXT_BY_SIZE(csize, hipLaunchKernelGGL((k_ext_bcast<U>), ext_grid(Tm->nvals), dim3(256), 0, ctx().stream, (U *)full, Tm->nvals, (const U *)Tm->d_val))
-                ctx().stats.kernel_launches += 1;
-                dev_free(Tm->d_val);
-                Tm->d_val = full;
-                Tm->iso = false;
-            } catch (...) {
-                matrix_free(Tm);
-                throw;
-            }
-        }
+        MatrixOwner Tm(matrix_cast_copy(S, ctype));
+        if (full_values) matrix_expand_iso(Tm.get());
         ctx().stats.out_nvals = Tm->nvals;
         return Tm;
     }
     const int method_run = (!J || run) ? 1 : 0;
-    GB_Matrix_opaque *Tm = matrix_new(type_of_code(ctype), ni, nj);
-    try {
-        const int64_t *Sp = S->d_ptr;
-        const int32_t *Sj = S->d_col;
-        const int64_t NI = (int64_t)ni, NJ = (int64_t)nj;
-        // ---- rows: segment, length and units of every output row; the two sums
-        const int64_t clo = J ? (int64_t)jmin : 0, chi = J ? (int64_t)jmax + 1 : n;  // the columns the call can select from: [clo, chi)
-        const bool narrow = clo > 0 || chi < n;
-        DevBuf<int64_t> seg((size_t)NI), lpre((size_t)NI + 1), ubase((size_t)NI + 1);
-        const uint64_t *Ip = I ? dI.p : nullptr;
-        if (narrow)
-            hipLaunchKernelGGL((k_ext_rowseg<true>), ext_grid(NI + 1), dim3(256), 0, ctx().stream, Sp, Sj, m, Ip, NI, clo, chi, seg.p, lpre.p, ubase.p);
-        else
-            hipLaunchKernelGGL((k_ext_rowseg<false>), ext_grid(NI + 1), dim3(256), 0, ctx().stream, Sp, Sj, m, Ip, NI, clo, chi, seg.p, lpre.p, ubase.p);
-        prim_exclusive_sum_i64(lpre.p, lpre.p, NI + 1);
-        prim_exclusive_sum_i64(ubase.p, ubase.p, NI + 1);
-        ctx().stats.kernel_launches += 3;
-        int64_t E = 0, nunits = 0;  // entries the call can select from, units
-        d2h(&E, lpre.p + NI, sizeof(int64_t));
-        d2h(&nunits, ubase.p + NI, sizeof(int64_t));
-        ctx().stats.tiles = nunits;
-        if (nunits > (int64_t)UINT32_MAX * 4) fail(GrB_NOT_IMPLEMENTED, "GrB_Matrix_extract: more than 2^34 units");
-        const dim3 ugrid((unsigned)std::max<int64_t>(1, ceil_div(nunits, 4)));
-        int64_t kept = 0;
-        DevPtr<int64_t> Tp;
-        DevPtr<int32_t> Tj;
-        DevPtr<char> raw;  // the kept values (one when t_iso) in S's type
-        auto alloc_out = [&](int64_t nnz) {
-            Tj.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnz));
-            raw.reset((char *)dev_alloc(ssize * (size_t)(t_iso ? 1 : nnz)));
-            if (t_iso) d2d(raw.p, S->d_val, ssize);
-        };
-        if (method_run) {
-            // ---- method 9: the segments ARE the output rows
-            ctx().stats.method = 9;
-            kept = E;
+    MatrixOwner Tm(matrix_new(type_of_code(ctype), ni, nj));
+    const int64_t *Sp = S->d_ptr;
+    const int32_t *Sj = S->d_col;
+    const int64_t NI = (int64_t)ni, NJ = (int64_t)nj;
+    // ---- rows: segment, length and units of every output row; the two sums
+    const int64_t clo = J ? (int64_t)jmin : 0, chi = J ? (int64_t)jmax + 1 : n;  // the columns the call can select from: [clo, chi)
+    const bool narrow = clo > 0 || chi < n;
+    DevBuf<int64_t> seg((size_t)NI), lpre((size_t)NI + 1), ubase((size_t)NI + 1);
+    const uint64_t *Ip = I ? dI.p : nullptr;
+    if (narrow)
+        hipLaunchKernelGGL((k_ext_rowseg<true>), grid1d(NI + 1), dim3(256), 0, ctx().stream, Sp, Sj, m, Ip, NI, clo, chi, seg.p, lpre.p, ubase.p);
+    else
+        hipLaunchKernelGGL((k_ext_rowseg<false>), grid1d(NI + 1), dim3(256), 0, ctx().stream, Sp, Sj, m, Ip, NI, clo, chi, seg.p, lpre.p, ubase.p);
+    prim_exclusive_sum_i64(lpre.p, lpre.p, NI + 1);
+    prim_exclusive_sum_i64(ubase.p, ubase.p, NI + 1);
+    ctx().stats.kernel_launches += 3;
+    int64_t E = 0, nunits = 0;  // entries the call can select from, units
+    d2h(&E, lpre.p + NI, sizeof(int64_t));
+    d2h(&nunits, ubase.p + NI, sizeof(int64_t));
+    ctx().stats.tiles = nunits;
+    if (nunits > (int64_t)UINT32_MAX * 4) fail(GrB_NOT_IMPLEMENTED, "GrB_Matrix_extract: more than 2^34 units");
+    const dim3 ugrid((unsigned)std::max<int64_t>(1, ceil_div(nunits, 4)));
+    int64_t kept = 0;
+    DevPtr<int64_t> Tp;
+    DevPtr<int32_t> Tj;
+    DevPtr<char> raw;  // the kept values (one when t_iso) in S's type
+    auto alloc_out = [&](int64_t nnz) {
+        Tj.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnz));
+        raw.reset((char *)dev_alloc(ssize * (size_t)(t_iso ? 1 : nnz)));
+        if (t_iso) d2d(raw.p, S->d_val, ssize);
+    };
+    if (method_run) {
+        // ---- method 9: the segments ARE the output rows
+        ctx().stats.method = 9;
+        kept = E;
+        if (kept > 0) {
+            alloc_out(kept);
+            GRB_DISPATCH_SIZE(ssize, U, hipLaunchKernelGGL((k_ext_copy<U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,
+                                                  (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (int32_t)clo, Tj.p,
+                                                  (U *)(t_iso ? nullptr : raw.p)))
+            ctx().stats.kernel_launches += 1;
+            Tp.reset(lpre.release());
+        }
+    } else if (nunits > 0) {
+        DevBuf<int64_t> upos((size_t)nunits + 1);
+        Tp.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(NI + 1)));
+        if (increasing) {
+            // ---- methods 10 / 11.  The table costs 4 * ncols bytes (written once, read at random); it is taken when that is no more than
+            // the (4 + sizeof T) * E bytes of columns and values the call reads anyway, so it never more than doubles the traffic.  A byte
+            // count, not a timing
+            const bool table = 4 * n <= (int64_t)(4 + ssize) * E;
+            ctx().stats.method = table ? 10 : 11;
+            DevBuf<int32_t> jinv(table ? (size_t)n : 0);
+            if (table) {
+                GRB_HIP(hipMemsetAsync(jinv.p, 0xff, sizeof(int32_t) * (size_t)n, ctx().stream));
+                hipLaunchKernelGGL(k_ext_jinv, grid1d(NJ), dim3(256), 0, ctx().stream, (const uint64_t *)dJ.p, NJ, n, jinv.p);
+                ctx().stats.kernel_launches += 2;
+            }
+#define EXT_PICK(TABLE, FILL, U, TJ, TX)                                                                                                              \
+hipLaunchKernelGGL((k_ext_pick<TABLE, FILL, U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,          \
+                   (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (const int32_t *)jinv.p, (const uint64_t *)dJ.p, NJ, upos.p, TJ, TX)
+            if (table) EXT_PICK(true, false, uint8_t, (int32_t *)nullptr, (uint8_t *)nullptr);
+            else EXT_PICK(false, false, uint8_t, (int32_t *)nullptr, (uint8_t *)nullptr);
+            prim_exclusive_sum_i64(upos.p, upos.p, nunits + 1);
+            ctx().stats.kernel_launches += 2;
+            d2h(&kept, upos.p + nunits, sizeof(int64_t));
             if (kept > 0) {
                 alloc_out(kept);
-                EXT_BY_SIZE(ssize, hipLaunchKernelGGL((k_ext_copy<U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,
-                                                      (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (int32_t)clo, Tj.p,
-                                                      (U *)(t_iso ? nullptr : raw.p)))
-                ctx().stats.kernel_launches += 1;
-                Tp.reset(lpre.release());
-            }
-        } else if (nunits > 0) {
-            DevBuf<int64_t> upos((size_t)nunits + 1);
-            Tp.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(NI + 1)));
-            if (increasing) {
-                // ---- methods 10 / 11.  The table costs 4 * ncols bytes (written once, read at random); it is taken when that is no more than
-                // the (4 + sizeof T) * E bytes of columns and values the call reads anyway, so it never more than doubles the traffic.  A byte
-                // count, not a timing
-                const bool table = 4 * n <= (int64_t)(4 + ssize) * E;
-                ctx().stats.method = table ? 10 : 11;
-                DevBuf<int32_t> jinv(table ? (size_t)n : 0);
-                if (table) {
-                    GRB_HIP(hipMemsetAsync(jinv.p, 0xff, sizeof(int32_t) * (size_t)n, ctx().stream));
-                    hipLaunchKernelGGL(k_ext_jinv, ext_grid(NJ), dim3(256), 0, ctx().stream, (const uint64_t *)dJ.p, NJ, n, jinv.p);
-                    ctx().stats.kernel_launches += 2;
-                }
-#define EXT_PICK(TABLE, FILL, U, TJ, TX)                                                                                                              \
-    hipLaunchKernelGGL((k_ext_pick<TABLE, FILL, U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,          \
-                       (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (const int32_t *)jinv.p, (const uint64_t *)dJ.p, NJ, upos.p, TJ, TX)
-                if (table) EXT_PICK(true, false, uint8_t, (int32_t *)nullptr, (uint8_t *)nullptr);
-                else EXT_PICK(false, false, uint8_t, (int32_t *)nullptr, (uint8_t *)nullptr);
-                prim_exclusive_sum_i64(upos.p, upos.p, nunits + 1);
+                hipLaunchKernelGGL(k_ext_rowptr, grid1d(NI + 1), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, (const int64_t *)upos.p, NI, Tp.p);
+                GRB_DISPATCH_SIZE(ssize, U, {
+                    U *tx = (U *)(t_iso ? nullptr : raw.p);
+                    if (table) EXT_PICK(true, true, U, Tj.p, tx);
+                    else EXT_PICK(false, true, U, Tj.p, tx);
+                })
                 ctx().stats.kernel_launches += 2;
-                d2h(&kept, upos.p + nunits, sizeof(int64_t));
-                if (kept > 0) {
-                    alloc_out(kept);
-                    hipLaunchKernelGGL(k_ext_rowptr, ext_grid(NI + 1), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, (const int64_t *)upos.p, NI, Tp.p);
-                    EXT_BY_SIZE(ssize, {
-                        U *tx = (U *)(t_iso ? nullptr : raw.p);
-                        if (table) EXT_PICK(true, true, U, Tj.p, tx);
-                        else EXT_PICK(false, true, U, Tj.p, tx);
-                    })
-                    ctx().stats.kernel_launches += 2;
-                }
+            }
 #undef EXT_PICK
-            } else {
-                // ---- method 12
-                ctx().stats.method = 12;
-                int cbits = 1;
-                while (cbits < 63 && (1ll << cbits) < n) cbits++;
-                DevBuf<uint64_t> sJ((size_t)NJ);
-                DevBuf<uint32_t> iota((size_t)NJ), perm((size_t)NJ);
-                hipLaunchKernelGGL(k_ext_iota, ext_grid(NJ), dim3(256), 0, ctx().stream, NJ, iota.p);
-                prim_sort_pairs_u64_u32((const uint64_t *)dJ.p, sJ.p, (const uint32_t *)iota.p, perm.p, NJ, cbits);
-#define EXT_DUP(FILL, U, KEY, PAY, VX)                                                                                                               \
-    hipLaunchKernelGGL((k_ext_dup<FILL, U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,                \
-                       (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (const uint64_t *)sJ.p, (const uint32_t *)perm.p, NJ, upos.p, KEY, PAY, VX)
-                EXT_DUP(false, uint8_t, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr);
-                prim_exclusive_sum_i64(upos.p, upos.p, nunits + 1);
-                ctx().stats.kernel_launches += 4;
-                d2h(&kept, upos.p + nunits, sizeof(int64_t));
-                if (kept >= (1ll << 32))
-                    fail(GrB_NOT_IMPLEMENTED, "GrB_Matrix_extract: an unsorted or repeating column list that selects 2^32 or more entries (" +
-                                                  std::to_string(kept) + ") is outside this library's path: sort the list, or extract in pieces");
-                if (kept > 0) {
-                    alloc_out(kept);
-                    hipLaunchKernelGGL(k_ext_rowptr, ext_grid(NI + 1), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, (const int64_t *)upos.p, NI, Tp.p);
-                    DevBuf<uint64_t> key((size_t)kept), key_s((size_t)kept);
-                    DevBuf<uint32_t> pay((size_t)kept), pay_s((size_t)kept);
-                    DevBuf<char> vx(t_iso ? 0 : ssize * (size_t)kept);
-                    EXT_BY_SIZE(ssize, EXT_DUP(true, U, key.p, pay.p, (U *)(t_iso ? nullptr : vx.p)))
-                    int rbits = 0;
-                    while ((1ll << rbits) < NI) rbits++;
-                    prim_sort_pairs_u64_u32((const uint64_t *)key.p, key_s.p, (const uint32_t *)pay.p, pay_s.p, kept, 32 + rbits);
-                    EXT_BY_SIZE(ssize, hipLaunchKernelGGL((k_ext_gather<U>), ext_grid(kept), dim3(256), 0, ctx().stream, (const uint64_t *)key_s.p,
-                                                          (const uint32_t *)pay_s.p, (const U *)vx.p, kept, Tj.p, (U *)(t_iso ? nullptr : raw.p)))
-                    ctx().stats.kernel_launches += 4;
-                }
-#undef EXT_DUP
-            }
         } else {
-            ctx().stats.method = increasing ? 11 : 12;  // (nothing to select from: no unit, no table)
-        }
-        if (kept > 0) {
-            const int64_t nv = t_iso ? 1 : kept;
-            if (stype == ctype) Tm->d_val = raw.release();
-            else {
-                Tm->d_val = dev_alloc(csize * (size_t)nv);
-                cast_array(ctype, Tm->d_val, stype, raw.p, nv);
+            // ---- method 12
+            ctx().stats.method = 12;
+            int cbits = 1;
+            while (cbits < 63 && (1ll << cbits) < n) cbits++;
+            DevBuf<uint64_t> sJ((size_t)NJ);
+            DevBuf<uint32_t> iota((size_t)NJ), perm((size_t)NJ);
+            hipLaunchKernelGGL(k_ext_iota, grid1d(NJ), dim3(256), 0, ctx().stream, NJ, iota.p);
+            prim_sort_pairs_u64_u32((const uint64_t *)dJ.p, sJ.p, (const uint32_t *)iota.p, perm.p, NJ, cbits);
+#define EXT_DUP(FILL, U, KEY, PAY, VX)                                                                                                               \
+hipLaunchKernelGGL((k_ext_dup<FILL, U>), ugrid, dim3(256), 0, ctx().stream, Sj, (const U *)S->d_val, a_iso, (const int64_t *)seg.p,                \
+                   (const int64_t *)lpre.p, (const int64_t *)ubase.p, NI, nunits, (const uint64_t *)sJ.p, (const uint32_t *)perm.p, NJ, upos.p, KEY, PAY, VX)
+            EXT_DUP(false, uint8_t, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr);
+            prim_exclusive_sum_i64(upos.p, upos.p, nunits + 1);
+            ctx().stats.kernel_launches += 4;
+            d2h(&kept, upos.p + nunits, sizeof(int64_t));
+            if (kept >= (1ll << 32))
+                fail(GrB_NOT_IMPLEMENTED, "GrB_Matrix_extract: an unsorted or repeating column list that selects 2^32 or more entries (" +
+                                              std::to_string(kept) + ") is outside this library's path: sort the list, or extract in pieces");
+            if (kept > 0) {
+                alloc_out(kept);
+                hipLaunchKernelGGL(k_ext_rowptr, grid1d(NI + 1), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, (const int64_t *)upos.p, NI, Tp.p);
+                DevBuf<uint64_t> key((size_t)kept), key_s((size_t)kept);
+                DevBuf<uint32_t> pay((size_t)kept), pay_s((size_t)kept);
+                DevBuf<char> vx(t_iso ? 0 : ssize * (size_t)kept);
+                GRB_DISPATCH_SIZE(ssize, U, EXT_DUP(true, U, key.p, pay.p, (U *)(t_iso ? nullptr : vx.p)))
+                int rbits = 0;
+                while ((1ll << rbits) < NI) rbits++;
+                prim_sort_pairs_u64_u32((const uint64_t *)key.p, key_s.p, (const uint32_t *)pay.p, pay_s.p, kept, 32 + rbits);
+                GRB_DISPATCH_SIZE(ssize, U, hipLaunchKernelGGL((k_ext_gather<U>), grid1d(kept), dim3(256), 0, ctx().stream, (const uint64_t *)key_s.p,
+                                                      (const uint32_t *)pay_s.p, (const U *)vx.p, kept, Tj.p, (U *)(t_iso ? nullptr : raw.p)))
+                ctx().stats.kernel_launches += 4;
             }
-            Tm->d_ptr = Tp.release();
-            Tm->d_col = Tj.release();
-            Tm->iso = t_iso;
-            Tm->nvals = kept;
+#undef EXT_DUP
         }
-        ctx().stats.out_nvals = kept;
-        GRB_HIP(hipGetLastError());
-        return Tm;
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
+    } else {
+        ctx().stats.method = increasing ? 11 : 12;  // (nothing to select from: no unit, no table)
     }
+    if (kept > 0) matrix_adopt(Tm.get(), Tp.release(), Tj.release(), raw.release(), stype, kept, t_iso);
+    ctx().stats.out_nvals = kept;
+    GRB_HIP(hipGetLastError());
+    return Tm;
 }
 
 static const uint64_t *ext_list(const uint64_t *L, const char *what)
@@ -541,33 +484,20 @@ static void matrix_extract(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB
     if (Mask) check_matrix(Mask, "Mask");
     I = ext_list(I, "I");
     J = ext_list(J, "J");
-    const bool t0 = desc && desc->t0;
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
-    const uint64_t in_rows = t0 ? A->ncols : A->nrows, in_cols = t0 ? A->nrows : A->ncols;
+    const MDesc f = mdesc_of(desc);
+    const uint64_t in_rows = f.t0 ? A->ncols : A->nrows, in_cols = f.t0 ? A->nrows : A->ncols;
     const uint64_t out_rows = I ? ni : in_rows, out_cols = J ? nj : in_cols;
     if (C->nrows != out_rows || C->ncols != out_cols)
         fail(GrB_DIMENSION_MISMATCH, "GrB_Matrix_extract: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the index lists select " +
                                          std::to_string(out_rows) + " x " + std::to_string(out_cols));
-    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "GrB_Matrix_extract: mask shape does not match the output");
-    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_Matrix_extract: accum operator type must equal the output type");
-    if (!Mask && comp) {  // complement of "no mask": nothing may be written
-        if (replace) matrix_release_storage(C);
-        return;
-    }
+    check_mask_accum("GrB_Matrix_extract", C, Mask, accum);
+    if (matrix_writes_nothing(C, Mask, f)) return;
     ctx().stats = GrX_Stats{};
-    GB_Matrix_opaque *S = t0 ? matrix_transpose_cached(A) : A;
-    // T is a fresh object, so C may alias A or the mask
-    GB_Matrix_opaque *Tm = extract_build(S, I, ni, J, nj, C->type->code, Mask || accum);
+    GB_Matrix_opaque *S = f.t0 ? matrix_transpose_cached(A) : A;
+    MatrixOwner Tm = extract_build(S, I, ni, J, nj, C->type->code, Mask || accum);
     const int64_t t_nvals = Tm->nvals;
-    try {
-        if (C == A) matrix_invalidate_caches(C);
-        matrix_apply_write_rule(C, Mask, accum, Tm, replace, comp, structure);
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
-    }
-    matrix_free(Tm);
-    ctx().stats.out_nvals = t_nvals;
+    matrix_finish(C, Mask, accum, std::move(Tm), f, C == A);
+    ctx().stats.out_nvals = t_nvals;  // (nnz(T), not nnz(C))
     sync_stream();  // (the index lists were host arrays borrowed for the call)
 }
 
@@ -609,19 +539,19 @@ static void col_extract(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bi
     ctx().stats.method = R ? 9 : 11;
     if (A->nvals == 0) {
         if (I) {
-            hipLaunchKernelGGL(k_ext_check, ext_grid((int64_t)n), dim3(256), 0, ctx().stream, (const uint64_t *)dI.p, (int64_t)n, dim, oob.p);
+            hipLaunchKernelGGL(k_ext_check, grid1d((int64_t)n), dim3(256), 0, ctx().stream, (const uint64_t *)dI.p, (int64_t)n, dim, oob.p);
             ctx().stats.kernel_launches += 1;
         }
     } else if (R) {
         int64_t e[2] = {0, 0};
         d2h(e, R->d_ptr + j, 2 * sizeof(int64_t));
         if (e[1] > e[0]) {
-            EXT_BY_SIZE(asize, hipLaunchKernelGGL((k_ext_rowscatter<U>), ext_grid(e[1] - e[0]), dim3(256), 0, ctx().stream, (const int32_t *)R->d_col,
+            GRB_DISPATCH_SIZE(asize, U, hipLaunchKernelGGL((k_ext_rowscatter<U>), grid1d(e[1] - e[0]), dim3(256), 0, ctx().stream, (const int32_t *)R->d_col,
                                                   (const U *)R->d_val, R->iso ? 1 : 0, e[0], e[1], (U *)t_val.p, (unsigned long long *)t_bits.p))
             ctx().stats.kernel_launches += 1;
         }
     } else {
-        EXT_BY_SIZE(asize, hipLaunchKernelGGL((k_ext_col<U>), ext_grid((int64_t)nwords * 64), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr,
+        GRB_DISPATCH_SIZE(asize, U, hipLaunchKernelGGL((k_ext_col<U>), grid1d((int64_t)nwords * 64), dim3(256), 0, ctx().stream, (const int64_t *)A->d_ptr,
                                               (const int32_t *)A->d_col, (const U *)A->d_val, a_iso, row_form ? 1 : 0, (int64_t)j,
                                               (const uint64_t *)(I ? dI.p : nullptr), (int64_t)n, dim, (U *)t_val.p, t_bits.p, oob.p))
         ctx().stats.kernel_launches += 1;
@@ -651,7 +581,7 @@ static bool matrix_element(GB_Matrix_opaque *A, uint64_t i, uint64_t j, unsigned
                                     " x " + std::to_string(A->ncols));
     if (A->nvals == 0) return false;
     DevBuf<unsigned long long> out(2);
-    EXT_BY_SIZE(A->type->size, hipLaunchKernelGGL((k_ext_element<U>), dim3(1), dim3(64), 0, ctx().stream, (const int64_t *)A->d_ptr, (const int32_t *)A->d_col,
+    GRB_DISPATCH_SIZE(A->type->size, U, hipLaunchKernelGGL((k_ext_element<U>), dim3(1), dim3(64), 0, ctx().stream, (const int64_t *)A->d_ptr, (const int32_t *)A->d_col,
                                                   (const U *)A->d_val, A->iso ? 1 : 0, (int64_t)i, (int32_t)j, out.p))
     unsigned long long h[2] = {0, 0};
     d2h(h, out.p, sizeof(h));

@@ -235,6 +235,13 @@ struct DevPtr {  // owner of a device block: a callee's result, or a member of a
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t bits_words64(uint64_t n) { return (size_t)((n + 63) / 64); }
+// the grid of a launch with one thread per item in workgroups of 256 (at least one workgroup)
+inline dim3 grid1d(int64_t threads)
+{
+    const int64_t g = threads > 256 ? ceil_div(threads, 256) : 1;
+    if (g > 0x7fffffff) fail(GrB_NOT_IMPLEMENTED, "problem too large for one launch");
+    return dim3((unsigned)g);
+}
 
 }  // namespace grb
 
@@ -317,6 +324,7 @@ void matrix_free(GB_Matrix_opaque *A);
 struct MatrixDeleter {
     void operator()(GB_Matrix_opaque *A) const { matrix_free(A); }
 };
+using MatrixOwner = std::unique_ptr<GB_Matrix_opaque, MatrixDeleter>;
 }  // namespace grb
 
 // The matrix object: what DESCRIBES the matrix (type, shape, CSR arrays, the hints `ranked` / `tr_of` / `hot_identity`, the cached transpose) as plain
@@ -434,7 +442,7 @@ struct GB_Matrix_opaque {
         bool short_tagged_only = false;    // the short part keeps its row pointers only: its entries live in the tagged row groups
         int64_t tails_max_len = 0;         // > 0: long rows with fewer entries than this have their cold entries in `short_part` (Context::cold_in_rows): the
                                            // short-row kernels add them up and MERGE the long-row accumulator into the row's result
-        std::unique_ptr<GB_Matrix_opaque, grb::MatrixDeleter> short_part;
+        grb::MatrixOwner short_part;
         int64_t n_long = 0, n_chunks = 0;
         grb::DevPtr<uint64_t> d_long_bits;    // bit r: row r is long
         grb::DevPtr<int32_t> d_long_rows;     // n_long row indices
@@ -564,6 +572,18 @@ GB_Matrix_opaque *matrix_transpose_cached(GB_Matrix_opaque *A);  // builds A->tr
 void cast_array(int dst_type, void *dst, int src_type, const void *src, int64_t n);
 // returns a matrix of `type` sharing structure (fresh values); caller frees with matrix_free.  nullptr if A already has that type.
 GB_Matrix_opaque *matrix_cast_copy(GB_Matrix_opaque *A, int type);
+// ---- the values of the fresh matrix T an operation builds ----
+// M's values in `type` (one value when M is iso): M's own array when the type matches or M is empty, else a cast copy that `hold` owns
+const void *values_as(const GB_Matrix_opaque *M, int type, DevPtr<char> &hold);
+// dst[0 .. n) = the n values of size `size` behind src: a copy, or -- iso -- src's one value n times (one launch, not counted here)
+void values_expanded(void *dst, const void *src, bool iso, int64_t n, size_t size);
+// T's values, held in type `from` (one value when iso), cast to type `to`, which becomes T's type: "T in the output type"
+void matrix_retype(GB_Matrix_opaque *T, int from, int to);
+// an iso T gets one value per entry (the write rule reads one per entry when it masks or accumulates); counts its launch in the stats
+void matrix_expand_iso(GB_Matrix_opaque *T);
+// T (empty, fresh) adopts a builder's compacted output: row pointers, columns, and the `kept` values `raw` (one when iso) in type
+// `raw_type`, cast to T's type when the two differ.  Takes ownership of the three arrays
+void matrix_adopt(GB_Matrix_opaque *T, int64_t *Tp, int32_t *Tj, void *raw, int raw_type, int64_t kept, bool iso);
 GB_Vector_opaque *vector_cast_copy(GB_Vector_opaque *v, int type);
 // out_bits = present(v) & (structure ? 1 : value != 0)
 void pack_bool_pv(const uint64_t *present, const bool *val, int64_t n, uint32_t *out);  // 2 bits per element: (present, value)
@@ -575,6 +595,26 @@ void pack_bool_values(const uint64_t *present, const bool *val, int64_t n, uint6
 // C<Mask, replace> = accum(C, T), T in C's type with sorted rows (grb_mxm.hip); takes T's storage when nothing masks or accumulates
 void matrix_apply_write_rule(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, GB_Matrix_opaque *T,
                              bool replace, bool comp, bool structure);
+
+// ---- the frame of an operation that builds a fresh matrix T and ends in the write rule (grb_mxm.hip) ----
+// In the caller's order: its own shape check, check_mask_accum, matrix_writes_nothing, build T in a MatrixOwner, matrix_finish.  When the
+// statistics are reset, what out_nvals reports and when the stream is synchronised differ between the operations and stay in the caller.
+struct MDesc {
+    bool replace = false, comp = false, structure = false, t0 = false, t1 = false;
+};
+inline MDesc mdesc_of(const GB_Descriptor_opaque *desc)
+{
+    MDesc f;
+    if (desc) { f.replace = desc->replace; f.comp = desc->comp; f.structure = desc->structure; f.t0 = desc->t0; f.t1 = desc->t1; }
+    return f;
+}
+// Mask has C's shape; accum is an operator of C's type and no comparison.  `op` prefixes the error text ("mxm", "GrB_select", ...)
+void check_mask_accum(const char *op, const GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum);
+// the complement of "no mask" allows no position: nothing may be written, and replace empties C.  true: the call is done
+bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MDesc f);
+// C<Mask, replace> = accum(C, T) for T in C's type; T is released on every way out.  c_is_an_input: C is also an operand, whose
+// cached layouts go before the write rule
+void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input);
 
 // ---- primitives implemented in grb_prim.hip (rocPRIM-backed) ---------------------------------------
 void prim_sort_pairs_u64_u32(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,

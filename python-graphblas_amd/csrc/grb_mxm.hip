@@ -2315,10 +2315,6 @@ static int64_t product_flops(GB_Matrix_opaque *A, GB_Matrix_opaque *B)
     return flops;
 }
 
-struct MDesc {
-    bool replace = false, comp = false, structure = false, t0 = false, t1 = false;
-};
-
 static void take_storage(GB_Matrix_opaque *C, GB_Matrix_opaque *src)
 {
     matrix_release_storage(C);
@@ -2340,56 +2336,42 @@ void matrix_apply_write_rule(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const 
         const int64_t *Tp = matrix_rowptr(Tm);
         const int acc_op = accum ? canonical_op(C->type->code, accum->op) : -1;
         const int64_t *Mp = Mask ? matrix_rowptr(Mask) : nullptr;
-        GB_Matrix_opaque *N = matrix_new(C->type, C->nrows, C->ncols);
+        MatrixOwner N_own(matrix_new(C->type, C->nrows, C->ncols));
+        GB_Matrix_opaque *N = N_own.get();
         if (ctx().mat_write_kernel == 1) {  // a wavefront per row / per column piece of a long row (grb_mxm_write.inc)
-            try {
-                WriteArgs wa{};
-                wa.m = m;
-                wa.Cp = (const int64_t *)C->d_ptr; wa.Cj = (const int32_t *)C->d_col; wa.Cx = C->d_val; wa.c_iso = C->iso ? 1 : 0;
-                wa.Tp = Tp; wa.Tj = (const int32_t *)Tm->d_col; wa.Tx = Tm->d_val;
-                wa.Mp = Mp; wa.Mj = Mask ? (const int32_t *)Mask->d_col : nullptr; wa.Mx = Mask ? (const void *)Mask->d_val : nullptr;
-                wa.m_type = Mask ? Mask->type->code : 0; wa.m_iso = Mask && Mask->iso ? 1 : 0; wa.has_mask = Mask ? 1 : 0;
-                wa.m_struct = f.structure ? 1 : 0; wa.m_comp = f.comp ? 1 : 0; wa.accum = acc_op; wa.replace = f.replace ? 1 : 0;
-                const int64_t ncols = (int64_t)C->ncols;
-                const int pieces = (int)std::min<int64_t>(WR_MAX_PIECES, std::max<int64_t>(1, ceil_div(ncols, (int64_t)16384)));
-                wa.piece_cols = (int)std::min<int64_t>(0x7fffffff, ceil_div(ncols, (int64_t)pieces));
-                DevBuf<int64_t> ubase(m + 1);
-                hipLaunchKernelGGL(k_write_units_per_row, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, wa.Cp, Tp, m, pieces, ubase.p);
-                prim_exclusive_sum_i64(ubase.p, ubase.p, m + 1);
-                int64_t n_units = 0, nnzN = 0;
-                d2h(&n_units, ubase.p + m, sizeof(int64_t));
-                if (n_units > 0) {
-                    DevBuf<int32_t> urow(n_units);
-                    hipLaunchKernelGGL(k_write_unit_rows, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, m, urow.p);
-                    DevBuf<int64_t> uoff(n_units + 1, true);
-                    wa.ubase = ubase.p; wa.urow = urow.p; wa.n_units = n_units; wa.ucount = uoff.p;
-                    const dim3 grid((unsigned)ceil_div(n_units, 4)), block(256);
-                    GRB_DISPATCH_TYPE(C->type->code, TW, { hipLaunchKernelGGL((k_mat_write_wave<TW, false>), grid, block, 0, ctx().stream, wa); })
-                    prim_exclusive_sum_i64(uoff.p, uoff.p, n_units + 1);
-                    d2h(&nnzN, uoff.p + n_units, sizeof(int64_t));
-                    if (nnzN) {
-                        N->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
-                        hipLaunchKernelGGL(k_write_rowptr, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p,
-                                           (const int64_t *)uoff.p, m, N->d_ptr);
-                        N->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzN);
-                        N->d_val = dev_alloc(C->type->size * (size_t)nnzN);
-                        wa.uoff = uoff.p; wa.Nj = N->d_col; wa.Nx = N->d_val;
-                        GRB_DISPATCH_TYPE(C->type->code, TW, { hipLaunchKernelGGL((k_mat_write_wave<TW, true>), grid, block, 0, ctx().stream, wa); })
-                    }
-                    ctx().stats.kernel_launches += 5;
-                    sync_stream();  // (the unit tables are released at the end of this scope)
+            WriteArgs wa{};
+            wa.m = m;
+            wa.Cp = (const int64_t *)C->d_ptr; wa.Cj = (const int32_t *)C->d_col; wa.Cx = C->d_val; wa.c_iso = C->iso ? 1 : 0;
+            wa.Tp = Tp; wa.Tj = (const int32_t *)Tm->d_col; wa.Tx = Tm->d_val;
+            wa.Mp = Mp; wa.Mj = Mask ? (const int32_t *)Mask->d_col : nullptr; wa.Mx = Mask ? (const void *)Mask->d_val : nullptr;
+            wa.m_type = Mask ? Mask->type->code : 0; wa.m_iso = Mask && Mask->iso ? 1 : 0; wa.has_mask = Mask ? 1 : 0;
+            wa.m_struct = f.structure ? 1 : 0; wa.m_comp = f.comp ? 1 : 0; wa.accum = acc_op; wa.replace = f.replace ? 1 : 0;
+            const UnitTable ut = unit_table(wa.Cp, Tp, m, (int64_t)C->ncols);
+            int64_t nnzN = 0;
+            if (ut.n_units > 0) {
+                DevBuf<int64_t> uoff(ut.n_units + 1, true);
+                wa.ubase = ut.ubase.p; wa.urow = ut.urow.p; wa.n_units = ut.n_units; wa.piece_cols = ut.piece_cols; wa.ucount = uoff.p;
+                const dim3 grid = ut.grid(), block(256);
+                GRB_DISPATCH_TYPE(C->type->code, TW, { hipLaunchKernelGGL((k_mat_write_wave<TW, false>), grid, block, 0, ctx().stream, wa); })
+                prim_exclusive_sum_i64(uoff.p, uoff.p, ut.n_units + 1);
+                d2h(&nnzN, uoff.p + ut.n_units, sizeof(int64_t));
+                if (nnzN) {
+                    N->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
+                    unit_table_rowptr(ut, uoff.p, m, N->d_ptr);
+                    N->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzN);
+                    N->d_val = dev_alloc(C->type->size * (size_t)nnzN);
+                    wa.uoff = uoff.p; wa.Nj = N->d_col; wa.Nx = N->d_val;
+                    GRB_DISPATCH_TYPE(C->type->code, TW, { hipLaunchKernelGGL((k_mat_write_wave<TW, true>), grid, block, 0, ctx().stream, wa); })
                 }
-                N->nvals = nnzN;
-                GRB_HIP(hipGetLastError());
-                take_storage(C, N);
-            } catch (...) {
-                matrix_free(N);
-                throw;
+                ctx().stats.kernel_launches += 5;
+                sync_stream();  // (the unit tables are released at the end of this scope)
             }
-            matrix_free(N);
+            N->nvals = nnzN;
+            GRB_HIP(hipGetLastError());
+            take_storage(C, N);
             return;
         }
-        try {
+        {
             DevBuf<int64_t> cnt(m + 1, true);
             int64_t *Np = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
             N->d_ptr = Np;
@@ -2425,12 +2407,28 @@ void matrix_apply_write_rule(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const 
             }
             sync_stream();
             take_storage(C, N);
-        } catch (...) {
-            matrix_free(N);
-            throw;
         }
-        matrix_free(N);
     }
+}
+
+void check_mask_accum(const char *op, const GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum)
+{
+    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, std::string(op) + ": mask shape does not match the output");
+    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op)))
+        fail(GrB_DOMAIN_MISMATCH, std::string(op) + ": accum operator type must equal the output type");
+}
+
+bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MDesc f)
+{
+    if (Mask || !f.comp) return false;
+    if (f.replace) matrix_release_storage(C);
+    return true;
+}
+
+void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input)
+{
+    if (c_is_an_input) matrix_invalidate_caches(C);  // (T is a fresh object: C may alias an operand or the mask)
+    matrix_apply_write_rule(C, Mask, accum, T.get(), f.replace, f.comp, f.structure);
 }
 
 static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum,
@@ -2440,33 +2438,15 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
     GB_Matrix_opaque *Be = f.t1 ? matrix_transpose_cached(B) : B;
     if (Ae->ncols != Be->nrows) fail(GrB_DIMENSION_MISMATCH, "mxm: inner dimensions " + std::to_string(Ae->ncols) + " and " + std::to_string(Be->nrows) + " differ");
     if (C->nrows != Ae->nrows || C->ncols != Be->ncols) fail(GrB_DIMENSION_MISMATCH, "mxm: output is " + std::to_string(C->nrows) + "x" + std::to_string(C->ncols) + ", product is " + std::to_string(Ae->nrows) + "x" + std::to_string(Be->ncols));
-    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "mxm: mask shape does not match the output");
-    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "mxm: accum operator type must equal the output type");
+    check_mask_accum("mxm", C, Mask, accum);
     ctx().stats = GrX_Stats{};
     ctx().stats.method = 3;
-    if (!Mask && f.comp) {
-        if (f.replace) matrix_release_storage(C);
-        return;
-    }
+    if (matrix_writes_nothing(C, Mask, f)) return;
     const int st = sr->type;
     const int monoid = canonical_op(st, sr->monoid), mult = canonical_op(st, sr->mult);
     // operands in the semiring's type
-    DevBuf<char> a_cast(0), b_cast(0);
-    const void *Ax = Ae->d_val, *Bx = Be->d_val;
-    if (Ae->nvals && Ae->type->code != st) {
-        const int64_t nv = Ae->iso ? 1 : Ae->nvals;
-        dev_free(a_cast.p);
-        a_cast.p = (char *)dev_alloc(type_size(st) * (size_t)nv);
-        cast_array(st, a_cast.p, Ae->type->code, Ae->d_val, nv);
-        Ax = a_cast.p;
-    }
-    if (Be->nvals && Be->type->code != st) {
-        const int64_t nv = Be->iso ? 1 : Be->nvals;
-        dev_free(b_cast.p);
-        b_cast.p = (char *)dev_alloc(type_size(st) * (size_t)nv);
-        cast_array(st, b_cast.p, Be->type->code, Be->d_val, nv);
-        Bx = b_cast.p;
-    }
+    DevPtr<char> a_cast, b_cast;
+    const void *Ax = values_as(Ae, st, a_cast), *Bx = values_as(Be, st, b_cast);
     GB_Matrix_opaque *Tm = nullptr;
     // A non-complemented mask bounds the useful part of the product by its own pattern: take the mask-driven path when the
     // full product would cost clearly more than walking it with the mask rows in LDS (always / never: option mxm_mask_mode)
@@ -2499,27 +2479,15 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
         if (fused) ctx().stats.method = 7;
     }
     if (!Tm) GRB_DISPATCH_TYPE(st, T, { Tm = spgemm<T>(Ae, Ax, Be, Bx, st, monoid, mult); })
-    try {
-        // T in the output type
-        if (Tm->nvals && Tm->type->code != C->type->code) {
-            void *cv = dev_alloc(C->type->size * (size_t)Tm->nvals);
-            cast_array(C->type->code, cv, st, Tm->d_val, Tm->nvals);
-            dev_free(Tm->d_val);
-            Tm->d_val = cv;
-        }
-        Tm->type = C->type;
-        // a mask-driven product lies inside the mask's pattern: under a structural mask, with nothing to accumulate into and
-        // nothing of C to keep (C empty, or replace), the write rule is C = T
-        // (the same for a fused complemented mask, valued or structural: T holds no forbidden position, and what C held at the
-        //  forbidden ones is either nothing or deleted by replace)
-        if (ctx().stats.method == 4 && !accum && f.structure && !f.comp && (C->nvals == 0 || f.replace)) take_storage(C, Tm);
-        else if (fused && !accum && (C->nvals == 0 || f.replace)) take_storage(C, Tm);
-        else matrix_apply_write_rule(C, Mask, accum, Tm, f.replace, f.comp, f.structure);
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
-    }
-    matrix_free(Tm);
+    MatrixOwner T_own(Tm);
+    matrix_retype(Tm, st, C->type->code);  // T in the output type
+    // a mask-driven product lies inside the mask's pattern: under a structural mask, with nothing to accumulate into and
+    // nothing of C to keep (C empty, or replace), the write rule is C = T
+    // (the same for a fused complemented mask, valued or structural: T holds no forbidden position, and what C held at the
+    //  forbidden ones is either nothing or deleted by replace)
+    if (ctx().stats.method == 4 && !accum && f.structure && !f.comp && (C->nvals == 0 || f.replace)) take_storage(C, Tm);
+    else if (fused && !accum && (C->nvals == 0 || f.replace)) take_storage(C, Tm);
+    else matrix_finish(C, Mask, accum, std::move(T_own), f, false);  // (take_storage drops C's cached layouts, as in the short cuts above)
     if (ctx().blocking) sync_stream();
 }
 
@@ -2537,62 +2505,31 @@ static void matrix_ewise_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const
     if (C->nrows != a_rows || C->ncols != a_cols)
         fail(GrB_DIMENSION_MISMATCH, "eWise: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the inputs " +
                                          std::to_string(a_rows) + " x " + std::to_string(a_cols));
-    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "eWise: mask shape does not match the output");
-    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "eWise: accum operator type must equal the output type");
+    check_mask_accum("eWise", C, Mask, accum);
     const bool cmp = op_is_comparison(op_in);
     const int op = cmp ? op_in : canonical_op(ot, op_in);
     const int tt = cmp ? (int)TC_BOOL : ot;  // type of the element-wise result
     ctx().stats = GrX_Stats{};
-    if (!Mask && f.comp) {  // complement of "no mask": nothing may be written
-        if (f.replace) matrix_release_storage(C);
-        return;
-    }
+    if (matrix_writes_nothing(C, Mask, f)) return;
     if (C->nrows == 0 || C->ncols == 0) return;
     GB_Matrix_opaque *Ae = f.t0 ? matrix_transpose_cached(A) : A;
     GB_Matrix_opaque *Be = f.t1 ? matrix_transpose_cached(B) : B;
     const int ctype = C->type->code;
-    GB_Matrix_opaque *Tm = nullptr;
+    MatrixOwner Tm;  // T in the output type
     if (Ae->nvals == 0 || Be->nvals == 0) {
         // exact short cuts: the intersection with nothing is empty, the union with nothing a cast copy of the other operand
         ctx().stats.method = 6;
-        if (!is_add || (Ae->nvals == 0 && Be->nvals == 0)) Tm = matrix_new(C->type, C->nrows, C->ncols);
+        if (!is_add || (Ae->nvals == 0 && Be->nvals == 0)) Tm.reset(matrix_new(C->type, C->nrows, C->ncols));
         else Tm = ewise_pass_through(Ae->nvals ? Ae : Be, ot, tt, ctype, Mask || accum);
     } else {
         ctx().stats.method = 8;
         // operands in the operator's type (an iso operand: its one value)
         DevPtr<char> a_cast, b_cast;
-        const void *Ax = Ae->d_val, *Bx = Be->d_val;
-        if (Ae->type->code != ot) {
-            const int64_t nv = Ae->iso ? 1 : Ae->nvals;
-            a_cast.p = (char *)dev_alloc(type_size(ot) * (size_t)nv);
-            cast_array(ot, a_cast.p, Ae->type->code, Ae->d_val, nv);
-            Ax = a_cast.p;
-        }
-        if (Be->type->code != ot) {
-            const int64_t nv = Be->iso ? 1 : Be->nvals;
-            b_cast.p = (char *)dev_alloc(type_size(ot) * (size_t)nv);
-            cast_array(ot, b_cast.p, Be->type->code, Be->d_val, nv);
-            Bx = b_cast.p;
-        }
+        const void *Ax = values_as(Ae, ot, a_cast), *Bx = values_as(Be, ot, b_cast);
         Tm = ewise_merge(Ae, Ax, Be, Bx, ot, tt, op, is_add, cmp);
+        matrix_retype(Tm.get(), tt, ctype);
     }
-    try {
-        // T in the output type
-        if (Tm->nvals && Tm->type->code != ctype) {
-            void *cv = dev_alloc(C->type->size * (size_t)Tm->nvals);
-            cast_array(ctype, cv, tt, Tm->d_val, Tm->nvals);
-            dev_free(Tm->d_val);
-            Tm->d_val = cv;
-        }
-        Tm->type = C->type;
-        // T is a fresh object, so C may alias A, B or the mask
-        if (C == A || C == B) matrix_invalidate_caches(C);
-        matrix_apply_write_rule(C, Mask, accum, Tm, f.replace, f.comp, f.structure);
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
-    }
-    matrix_free(Tm);
+    matrix_finish(C, Mask, accum, std::move(Tm), f, C == A || C == B);
     ctx().stats.out_nvals = C->nvals;
     if (ctx().blocking) sync_stream();
 }
@@ -2763,9 +2700,7 @@ extern "C" GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
     check_matrix(A, "A");
     check_matrix(B, "B");
     if (!semiring) fail(GrB_NULL_POINTER, "semiring is NULL");
-    MDesc f;
-    if (desc) { f.replace = desc->replace; f.comp = desc->comp; f.structure = desc->structure; f.t0 = desc->t0; f.t1 = desc->t1; }
-    mxm_core(C, Mask, accum, semiring, A, B, f);
+    mxm_core(C, Mask, accum, semiring, A, B, mdesc_of(desc));
     GRB_CATCH(errp(C))
 }
 
@@ -2781,9 +2716,7 @@ extern "C" GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
         check_matrix(A, "A");                                                                                                     \
         check_matrix(B, "B");                                                                                                     \
         if (!op) fail(GrB_NULL_POINTER, "eWise: operator is NULL");                                                               \
-        MDesc f;                                                                                                                  \
-        if (desc) { f.replace = desc->replace; f.comp = desc->comp; f.structure = desc->structure; f.t0 = desc->t0; f.t1 = desc->t1; } \
-        matrix_ewise_core(C, Mask, accum, op->CODE, op->type, A, B, f, IS_ADD);                                                  \
+        matrix_ewise_core(C, Mask, accum, op->CODE, op->type, A, B, mdesc_of(desc), IS_ADD);                                     \
         GRB_CATCH(errp(C))                                                                                                        \
     }
 GRB_MATRIX_EWISE(GrB_Matrix_eWiseAdd_BinaryOp, GrB_BinaryOp, op, true)

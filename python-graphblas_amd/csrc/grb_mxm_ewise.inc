@@ -141,13 +141,6 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
     if (!FILL && lane == 0) a.ucount[unit] = cnt;
 }
 
-template <typename U>
-__global__ void k_ewise_bcast(U *out, int64_t n, const U *src)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = src[0];
-}
-
 template <typename T>
 static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea)
 {
@@ -163,100 +156,54 @@ static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs 
 
 // T (fresh storage, type `tt`) = A (op) B; Ax / Bx: the operands' values in the operator's type `ot` (one value when iso); both
 // operands hold entries
-static GB_Matrix_opaque *ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op,
-                                     bool is_add, bool cmp)
+static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op, bool is_add, bool cmp)
 {
-    GB_Matrix_opaque *Tm = matrix_new(type_of_code(tt), A->nrows, A->ncols);
-    try {
-        const int64_t m = (int64_t)A->nrows, ncols = (int64_t)A->ncols;
-        EwiseArgs ea{};
-        ea.Ap = A->d_ptr; ea.Aj = A->d_col; ea.Ax = Ax; ea.a_iso = A->iso ? 1 : 0;
-        ea.Bp = B->d_ptr; ea.Bj = B->d_col; ea.Bx = Bx; ea.b_iso = B->iso ? 1 : 0;
-        ea.op = op;
-        const int pieces = (int)std::min<int64_t>(WR_MAX_PIECES, std::max<int64_t>(1, ceil_div(ncols, (int64_t)16384)));
-        ea.piece_cols = (int)std::min<int64_t>(0x7fffffff, ceil_div(ncols, (int64_t)pieces));
-        DevBuf<int64_t> ubase(m + 1);
-        hipLaunchKernelGGL(k_write_units_per_row, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, ea.Ap, ea.Bp, m, pieces, ubase.p);
-        prim_exclusive_sum_i64(ubase.p, ubase.p, m + 1);
-        int64_t n_units = 0, nnzT = 0;
-        d2h(&n_units, ubase.p + m, sizeof(int64_t));
-        if (n_units == 0) {
-            ctx().stats.kernel_launches += 2;
-            return Tm;
-        }
-        DevBuf<int32_t> urow(n_units);
-        hipLaunchKernelGGL(k_write_unit_rows, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p, m, urow.p);
-        DevBuf<int64_t> uoff(n_units + 1, true);
-        ea.ubase = ubase.p; ea.urow = urow.p; ea.n_units = n_units; ea.ucount = uoff.p;
-        const dim3 grid((unsigned)ceil_div(n_units, 4)), block(256);
-        // (the count pass reads no value: one instantiation per pattern rule)
-        if (is_add) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false>), grid, block, 0, ctx().stream, ea);
-        else hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, false, false, false>), grid, block, 0, ctx().stream, ea);
-        prim_exclusive_sum_i64(uoff.p, uoff.p, n_units + 1);
-        d2h(&nnzT, uoff.p + n_units, sizeof(int64_t));
-        ctx().stats.kernel_launches += 5;
-        if (nnzT) {
-            Tm->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
-            hipLaunchKernelGGL(k_write_rowptr, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ubase.p,
-                               (const int64_t *)uoff.p, m, Tm->d_ptr);
-            Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzT);
-            Tm->d_val = dev_alloc(type_size(tt) * (size_t)nnzT);
-            ea.uoff = uoff.p; ea.Tj = Tm->d_col; ea.Tx = Tm->d_val;
-            GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea); })
-            ctx().stats.kernel_launches += 2;
-        }
-        Tm->nvals = nnzT;
-        GRB_HIP(hipGetLastError());
-        sync_stream();  // (the unit tables are released at the end of this scope)
+    MatrixOwner Tm(matrix_new(type_of_code(tt), A->nrows, A->ncols));
+    const int64_t m = (int64_t)A->nrows;
+    EwiseArgs ea{};
+    ea.Ap = A->d_ptr; ea.Aj = A->d_col; ea.Ax = Ax; ea.a_iso = A->iso ? 1 : 0;
+    ea.Bp = B->d_ptr; ea.Bj = B->d_col; ea.Bx = Bx; ea.b_iso = B->iso ? 1 : 0;
+    ea.op = op;
+    const UnitTable ut = unit_table(ea.Ap, ea.Bp, m, (int64_t)A->ncols);
+    if (ut.n_units == 0) {
+        ctx().stats.kernel_launches += 2;
         return Tm;
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
     }
+    int64_t nnzT = 0;
+    DevBuf<int64_t> uoff(ut.n_units + 1, true);
+    ea.ubase = ut.ubase.p; ea.urow = ut.urow.p; ea.n_units = ut.n_units; ea.piece_cols = ut.piece_cols; ea.ucount = uoff.p;
+    const dim3 grid = ut.grid(), block(256);
+    // (the count pass reads no value: one instantiation per pattern rule)
+    if (is_add) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false>), grid, block, 0, ctx().stream, ea);
+    else hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, false, false, false>), grid, block, 0, ctx().stream, ea);
+    prim_exclusive_sum_i64(uoff.p, uoff.p, ut.n_units + 1);
+    d2h(&nnzT, uoff.p + ut.n_units, sizeof(int64_t));
+    ctx().stats.kernel_launches += 5;
+    if (nnzT) {
+        Tm->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (m + 1));
+        unit_table_rowptr(ut, uoff.p, m, Tm->d_ptr);
+        Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzT);
+        Tm->d_val = dev_alloc(type_size(tt) * (size_t)nnzT);
+        ea.uoff = uoff.p; ea.Tj = Tm->d_col; ea.Tx = Tm->d_val;
+        GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea); })
+        ctx().stats.kernel_launches += 2;
+    }
+    Tm->nvals = nnzT;
+    GRB_HIP(hipGetLastError());
+    sync_stream();  // (the unit tables are released at the end of this scope)
+    return Tm;
 }
 
 // T = the entries of S as eWiseAdd passes them through when the other operand is empty: cast to the operator's type `ot`, to the
 // element-wise result type `tt`, then to `ctype`.  full_values: one value per entry even when S is iso (the write rule reads one value
 // per entry of T when it masks or accumulates)
-static GB_Matrix_opaque *ewise_pass_through(GB_Matrix_opaque *S, int ot, int tt, int ctype, bool full_values)
+static MatrixOwner ewise_pass_through(GB_Matrix_opaque *S, int ot, int tt, int ctype, bool full_values)
 {
-    GB_Matrix_opaque *Tm = matrix_cast_copy(S, ot);
-    if (Tm->nvals == 0) {
-        Tm->type = type_of_code(ctype);
-        return Tm;
-    }
-    try {
-        const int64_t nv = Tm->iso ? 1 : Tm->nvals;
-        int cur = ot;
-        for (const int next : {tt, ctype}) {
-            if (next == cur) continue;
-            void *nvp = dev_alloc(type_size(next) * (size_t)nv);
-            cast_array(next, nvp, cur, Tm->d_val, nv);
-            dev_free(Tm->d_val);
-            Tm->d_val = nvp;
-            cur = next;
-        }
-        Tm->type = type_of_code(ctype);
-        if (Tm->iso && full_values) {
-            const size_t size = type_size(ctype);
-            const int64_t n = Tm->nvals;
-            void *full = dev_alloc(size * (size_t)n);
-            const dim3 grid((unsigned)ceil_div(n, 256)), block(256);
-            switch (size) {
-            case 1: hipLaunchKernelGGL((k_ewise_bcast<uint8_t>), grid, block, 0, ctx().stream, (uint8_t *)full, n, (const uint8_t *)Tm->d_val); break;
-            case 2: hipLaunchKernelGGL((k_ewise_bcast<uint16_t>), grid, block, 0, ctx().stream, (uint16_t *)full, n, (const uint16_t *)Tm->d_val); break;
-            case 4: hipLaunchKernelGGL((k_ewise_bcast<uint32_t>), grid, block, 0, ctx().stream, (uint32_t *)full, n, (const uint32_t *)Tm->d_val); break;
-            default: hipLaunchKernelGGL((k_ewise_bcast<uint64_t>), grid, block, 0, ctx().stream, (uint64_t *)full, n, (const uint64_t *)Tm->d_val); break;
-            }
-            ctx().stats.kernel_launches += 1;
-            dev_free(Tm->d_val);
-            Tm->d_val = full;
-            Tm->iso = false;
-        }
-        GRB_HIP(hipGetLastError());
-        return Tm;
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
-    }
+    MatrixOwner Tm(matrix_cast_copy(S, ot));
+    matrix_retype(Tm.get(), ot, tt);
+    matrix_retype(Tm.get(), tt, ctype);
+    if (full_values) matrix_expand_iso(Tm.get());
+    GRB_HIP(hipGetLastError());
+    return Tm;
 }
+

@@ -68,6 +68,37 @@ __global__ void k_write_rowptr(const int64_t *ubase, const int64_t *uoff, int64_
     if (i <= m) Np[i] = uoff[ubase[i]];
 }
 
+// The unit table of a merge of two sorted lists per row (the write rule: C_old and T; eWise: A and B), shared by both kernels
+struct UnitTable {
+    DevPtr<int64_t> ubase;  // first unit of every row (m + 1)
+    DevPtr<int32_t> urow;   // the row of every unit (nullptr without units)
+    int64_t n_units = 0;
+    int piece_cols = 0;     // columns per piece of a cut row
+    dim3 grid() const { return dim3((unsigned)ceil_div(n_units, 4)); }  // a wavefront per unit, four to a workgroup
+};
+// units of the m rows of the lists with row pointers Xp (nullptr: an empty list) and Yp over `ncols` columns: two launches, three
+// when there are units (the callers count them)
+static UnitTable unit_table(const int64_t *Xp, const int64_t *Yp, int64_t m, int64_t ncols)
+{
+    UnitTable ut;
+    const int pieces = (int)std::min<int64_t>(WR_MAX_PIECES, std::max<int64_t>(1, ceil_div(ncols, (int64_t)16384)));
+    ut.piece_cols = (int)std::min<int64_t>(0x7fffffff, ceil_div(ncols, (int64_t)pieces));
+    ut.ubase.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1)));
+    hipLaunchKernelGGL(k_write_units_per_row, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, Xp, Yp, m, pieces, ut.ubase.p);
+    prim_exclusive_sum_i64(ut.ubase.p, ut.ubase.p, m + 1);
+    d2h(&ut.n_units, ut.ubase.p + m, sizeof(int64_t));
+    if (ut.n_units > 0) {
+        ut.urow.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)ut.n_units));
+        hipLaunchKernelGGL(k_write_unit_rows, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ut.ubase.p, m, ut.urow.p);
+    }
+    return ut;
+}
+// Np[i] = where row i's first unit writes: uoff = the exclusive sum of the units' counts
+static void unit_table_rowptr(const UnitTable &ut, const int64_t *uoff, int64_t m, int64_t *Np)
+{
+    hipLaunchKernelGGL(k_write_rowptr, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, (const int64_t *)ut.ubase.p, uoff, m, Np);
+}
+
 // first position p in [lo, hi) with a[p] >= key (hi if none), searched by the whole wavefront: 64 probes per round trip
 __device__ __forceinline__ int64_t wave_lower_bound(const int32_t *a, int64_t lo, int64_t hi, int key, int lane)
 {

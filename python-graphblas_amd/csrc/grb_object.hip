@@ -15,14 +15,7 @@
 namespace grb {
 
 static constexpr int BS = 256;
-static inline dim3 grid_for(int64_t n, int per_block = BS)
-{
-    int64_t g = ceil_div(n, per_block);
-    if (g < 1) g = 1;
-    if (g > 0x7fffffff) fail(GrB_NOT_IMPLEMENTED, "problem too large for one launch");
-    return dim3((unsigned)g);
-}
-#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, grid_for(n), dim3(BS), 0, ctx().stream, __VA_ARGS__)
+#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, grid1d(n), dim3(BS), 0, ctx().stream, __VA_ARGS__)
 
 // ---------------------------------------------------------------------------------------------------
 // kernels
@@ -369,22 +362,13 @@ void vector_set_order(GB_Vector_opaque *v, GB_Perm *order)
                 // forward maps: into an order, element i goes to position d_rank[i]; back, position p goes to element d_inv[p]
                 const int32_t *dst_of = order ? order->d_rank : v->order->d_inv;
                 const int64_t threads = (int64_t)bits_words64(v->n);
-                switch (v->type->size) {
-                case 1: LAUNCH((k_vec_permute_sparse<uint8_t>), threads, n, dst_of, (const uint8_t *)v->d_val, (const uint64_t *)v->d_bits, (uint8_t *)nval, (unsigned long long *)nbits); break;
-                case 2: LAUNCH((k_vec_permute_sparse<uint16_t>), threads, n, dst_of, (const uint16_t *)v->d_val, (const uint64_t *)v->d_bits, (uint16_t *)nval, (unsigned long long *)nbits); break;
-                case 4: LAUNCH((k_vec_permute_sparse<uint32_t>), threads, n, dst_of, (const uint32_t *)v->d_val, (const uint64_t *)v->d_bits, (uint32_t *)nval, (unsigned long long *)nbits); break;
-                default: LAUNCH((k_vec_permute_sparse<uint64_t>), threads, n, dst_of, (const uint64_t *)v->d_val, (const uint64_t *)v->d_bits, (uint64_t *)nval, (unsigned long long *)nbits); break;
-                }
+                GRB_DISPATCH_SIZE(v->type->size, U, LAUNCH((k_vec_permute_sparse<U>), threads, n, dst_of, (const U *)v->d_val, (const uint64_t *)v->d_bits, (U *)nval,
+                                                           (unsigned long long *)nbits))
             } else {
                 // inverse maps: into an order, position p takes the element d_inv[p]; back, element i comes from position d_rank[i]
                 const int32_t *src_of = order ? order->d_inv : v->order->d_rank;
                 const int64_t threads = (int64_t)bits_words64(v->n) * 64;
-                switch (v->type->size) {
-                case 1: LAUNCH((k_vec_permute<uint8_t>), threads, n, src_of, (const uint8_t *)v->d_val, (const uint64_t *)v->d_bits, (uint8_t *)nval, nbits); break;
-                case 2: LAUNCH((k_vec_permute<uint16_t>), threads, n, src_of, (const uint16_t *)v->d_val, (const uint64_t *)v->d_bits, (uint16_t *)nval, nbits); break;
-                case 4: LAUNCH((k_vec_permute<uint32_t>), threads, n, src_of, (const uint32_t *)v->d_val, (const uint64_t *)v->d_bits, (uint32_t *)nval, nbits); break;
-                default: LAUNCH((k_vec_permute<uint64_t>), threads, n, src_of, (const uint64_t *)v->d_val, (const uint64_t *)v->d_bits, (uint64_t *)nval, nbits); break;
-                }
+                GRB_DISPATCH_SIZE(v->type->size, U, LAUNCH((k_vec_permute<U>), threads, n, src_of, (const U *)v->d_val, (const uint64_t *)v->d_bits, (U *)nval, nbits))
             }
         } catch (...) {
             vector_free_pair(v->padded, nval, nbits);
@@ -790,16 +774,6 @@ static void matrix_build_typed(GB_Matrix_opaque *C, const uint64_t *I, const uin
     matrix_build_device<T>(C, dI.p, dJ.p, dX.p, n, dup, "GrB_Matrix_build");
 }
 
-// full-length device copy of A's values (expands iso)
-template <typename T>
-static T *matrix_values_expanded(GB_Matrix_opaque *A)
-{
-    T *out = (T *)dev_alloc(sizeof(T) * (size_t)(A->nvals ? A->nvals : 1));
-    if (A->iso) LAUNCH((k_fill<T>), A->nvals, out, A->nvals, (const T *)A->d_val);
-    else d2d(out, A->d_val, sizeof(T) * (size_t)A->nvals);
-    return out;
-}
-
 template <typename T>
 static void matrix_extract_typed(GB_Matrix_opaque *A, uint64_t *I, uint64_t *J, void *X, int x_type, uint64_t *nvals_io)
 {
@@ -819,12 +793,12 @@ static void matrix_extract_typed(GB_Matrix_opaque *A, uint64_t *I, uint64_t *J, 
         d2h(J, cols.p, sizeof(uint64_t) * nv);
     }
     if (X) {
-        DevPtr<T> vals_own(matrix_values_expanded<T>(A));
-        T *vals = vals_own.p;
-        if (x_type == A->type->code) d2h(X, vals, sizeof(T) * nv);
+        DevBuf<T> vals(nv);
+        values_expanded(vals.p, A->d_val, A->iso, nv, sizeof(T));
+        if (x_type == A->type->code) d2h(X, vals.p, sizeof(T) * nv);
         else {
             DevBuf<char> c((size_t)nv * type_size(x_type));
-            cast_array(x_type, c.p, A->type->code, vals, nv);
+            cast_array(x_type, c.p, A->type->code, vals.p, nv);
             d2h(X, c.p, (size_t)nv * type_size(x_type));
         }
     }
@@ -887,6 +861,64 @@ GB_Matrix_opaque *matrix_cast_copy(GB_Matrix_opaque *A, int type)
 }
 
 static GB_Matrix_opaque *matrix_dup(GB_Matrix_opaque *A) { return matrix_cast_copy(A, A->type->code); }
+
+// ---- the values of a fresh result T (declared in grb_internal.hpp) ----
+const void *values_as(const GB_Matrix_opaque *M, int type, DevPtr<char> &hold)
+{
+    if (M->nvals == 0 || M->type->code == type) return M->d_val;
+    const int64_t nv = M->iso ? 1 : M->nvals;
+    hold.reset((char *)dev_alloc(type_size(type) * (size_t)nv));
+    cast_array(type, hold.p, M->type->code, M->d_val, nv);
+    return hold.p;
+}
+
+void values_expanded(void *dst, const void *src, bool iso, int64_t n, size_t size)
+{
+    if (n <= 0) return;
+    if (!iso) d2d(dst, src, size * (size_t)n);
+    else GRB_DISPATCH_SIZE(size, U, LAUNCH((k_fill<U>), n, (U *)dst, n, (const U *)src))
+}
+
+void matrix_retype(GB_Matrix_opaque *T, int from, int to)
+{
+    if (T->nvals && from != to) {
+        const int64_t nv = T->iso ? 1 : T->nvals;
+        DevPtr<char> cv((char *)dev_alloc(type_size(to) * (size_t)nv));
+        cast_array(to, cv.p, from, T->d_val, nv);
+        dev_free(T->d_val);
+        T->d_val = cv.release();
+    }
+    T->type = type_of_code(to);
+}
+
+void matrix_expand_iso(GB_Matrix_opaque *T)
+{
+    if (!T->iso) return;
+    if (T->nvals) {
+        const size_t size = T->type->size;
+        DevPtr<char> full((char *)dev_alloc(size * (size_t)T->nvals));
+        values_expanded(full.p, T->d_val, true, T->nvals, size);
+        ctx().stats.kernel_launches += 1;
+        dev_free(T->d_val);
+        T->d_val = full.release();
+    }
+    T->iso = false;
+}
+
+void matrix_adopt(GB_Matrix_opaque *T, int64_t *Tp, int32_t *Tj, void *raw, int raw_type, int64_t kept, bool iso)
+{
+    DevPtr<char> own((char *)raw);
+    T->d_ptr = Tp;  // (T owns them from here: whoever holds T releases them if the cast below throws)
+    T->d_col = Tj;
+    const int64_t nv = iso ? 1 : kept;
+    if (raw_type == T->type->code) T->d_val = own.release();
+    else {
+        T->d_val = dev_alloc(T->type->size * (size_t)nv);
+        cast_array(T->type->code, T->d_val, raw_type, own.p, nv);
+    }
+    T->iso = iso;
+    T->nvals = kept;
+}
 
 // import host CSR/CSC (uint64 pointers and indices) into the (empty) matrix A.  Entries inside a row need not be sorted.
 // iso: Ax holds ONE value that every entry takes (the GxB import / pack forms; GrB_Matrix_import has no such flag).
@@ -1256,35 +1288,16 @@ extern "C" GrB_Info GrB_transpose(GrB_Matrix C, const GrB_Matrix Mask, const GrB
     check_matrix(C, "C");
     check_matrix(A, "A");
     if (Mask) check_matrix(Mask, "Mask");
-    const bool t0 = desc && desc->t0;
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
-    GB_Matrix_opaque *S = t0 ? A : matrix_transpose_cached(A);  // transposing a transpose is a copy
+    const MDesc f = mdesc_of(desc);
+    GB_Matrix_opaque *S = f.t0 ? A : matrix_transpose_cached(A);  // transposing a transpose is a copy
     if (C->nrows != S->nrows || C->ncols != S->ncols) fail(GrB_DIMENSION_MISMATCH, "GrB_transpose: output shape mismatch");
-    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "GrB_transpose: mask shape does not match the output");
-    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_transpose: accum operator type must equal the output type");
-    if (!Mask && comp) {  // complement of "no mask": nothing may be written
-        if (replace) matrix_release_storage(C);
-        return GrB_SUCCESS;
-    }
+    check_mask_accum("GrB_transpose", C, Mask, accum);
+    if (matrix_writes_nothing(C, Mask, f)) return GrB_SUCCESS;
     // T = the (transposed) copy in C's type -- a fresh object, so C may alias A or the mask -- then the write rule
-    // (reference core/base.py:401-411: C(mask, accum, replace) << A.T)
-    GB_Matrix_opaque *copy = matrix_cast_copy(S, C->type->code);
-    if (copy->iso && copy->nvals && (Mask || accum)) {  // (the write rule reads one value per entry)
-        GRB_DISPATCH_TYPE(C->type->code, TC_, {
-            void *full = matrix_values_expanded<TC_>(copy);
-            dev_free(copy->d_val);
-            copy->d_val = full;
-        })
-        copy->iso = false;
-    }
-    try {
-        if (C == A) matrix_invalidate_caches(C);
-        matrix_apply_write_rule(C, Mask, accum, copy, replace, comp, structure);
-    } catch (...) {
-        matrix_free(copy);
-        throw;
-    }
-    matrix_free(copy);
+    // (reference core/base.py:401-411: C(mask, accum, replace) << A.T).  The statistics of the previous call are not reset
+    MatrixOwner copy(matrix_cast_copy(S, C->type->code));
+    if (Mask || accum) matrix_expand_iso(copy.get());
+    matrix_finish(C, Mask, accum, std::move(copy), f, C == A);
     GRB_CATCH(errp(C))
 }
 

@@ -201,6 +201,27 @@ GRB_HD D cast_value(S s)
     }
 #endif
 
+// values that are moved, not read: U = the unsigned integer of the value size
+#define GRB_DISPATCH_SIZE(size, U, ...)                     \
+    switch (size) {                                         \
+    case 1: { using U = uint8_t; __VA_ARGS__; } break;      \
+    case 2: { using U = uint16_t; __VA_ARGS__; } break;     \
+    case 4: { using U = uint32_t; __VA_ARGS__; } break;     \
+    default: { using U = uint64_t; __VA_ARGS__; } break;    \
+    }
+
+// first p in [lo, hi) with a[p] >= key (hi if none): a sorted ascending
+template <typename K>
+__device__ __forceinline__ int64_t lower_bound(const K *__restrict__ a, int64_t lo, int64_t hi, K key)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // ---- accumulator helpers (device only) ----------------------------------------------------------------
 template <typename T, typename W>
 __device__ __forceinline__ T from_acc(W v)

@@ -178,13 +178,6 @@ __global__ void k_select_rowslice(const int64_t *__restrict__ Ap, int64_t m, int
     Np[i] = p - lo;
 }
 
-template <typename U>
-__global__ void k_select_bcast(U *out, int64_t n, const U *src)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = src[0];
-}
-
 // ---- vector form: one element-wise pass over values and presence words (the style of grb_vecops.hip) ---------------------------------
 template <int OP, typename T>
 __global__ void k_vselect(int64_t n, const T *__restrict__ val, const uint64_t *__restrict__ bits, int64_t k, T y, uint64_t *__restrict__ t_bits)
@@ -200,8 +193,6 @@ __global__ void k_vselect(int64_t n, const T *__restrict__ val, const uint64_t *
     const unsigned long long b = __ballot(pred);
     if (lane == 0 && g < ((n + 63) >> 6)) t_bits[g] = b;
 }
-
-static dim3 grid1(int64_t threads) { return dim3((unsigned)std::max<int64_t>(1, ceil_div(threads, 256))); }
 
 // (ROWLE / ROWGT of a matrix never reach the flag pass: they are a slice of the row pointers)
 #define SEL_FOR_POS_FLAG(X) X(SEL_TRIL) X(SEL_TRIU) X(SEL_DIAG) X(SEL_OFFDIAG) X(SEL_COLLE) X(SEL_COLGT)
@@ -255,142 +246,99 @@ static int sel_trivial(int op, int64_t m, int64_t n, int64_t k)
     }
 }
 
-static void move_values(void *dst, const void *src, int a_iso, int64_t n, size_t size)
-{
-    if (n <= 0) return;
-    if (!a_iso) {
-        d2d(dst, src, size * (size_t)n);
-        return;
-    }
-    switch (size) {
-    case 1: hipLaunchKernelGGL((k_select_bcast<uint8_t>), grid1(n), dim3(256), 0, ctx().stream, (uint8_t *)dst, n, (const uint8_t *)src); break;
-    case 2: hipLaunchKernelGGL((k_select_bcast<uint16_t>), grid1(n), dim3(256), 0, ctx().stream, (uint16_t *)dst, n, (const uint16_t *)src); break;
-    case 4: hipLaunchKernelGGL((k_select_bcast<uint32_t>), grid1(n), dim3(256), 0, ctx().stream, (uint32_t *)dst, n, (const uint32_t *)src); break;
-    default: hipLaunchKernelGGL((k_select_bcast<uint64_t>), grid1(n), dim3(256), 0, ctx().stream, (uint64_t *)dst, n, (const uint64_t *)src); break;
-    }
-    ctx().stats.kernel_launches += 1;
-}
-
 // T (of type `ctype`, fresh storage) = the entries of S the operator keeps.  full_values: one value per entry even when S is iso
 // (the write rule reads one value per entry when it masks or accumulates)
-static GB_Matrix_opaque *select_build(GB_Matrix_opaque *S, const GB_IndexUnaryOp_opaque *op, const Thunk &th, int ctype, bool full_values)
+static MatrixOwner select_build(GB_Matrix_opaque *S, const GB_IndexUnaryOp_opaque *op, const Thunk &th, int ctype, bool full_values)
 {
-    GB_Matrix_opaque *Tm = matrix_new(type_of_code(ctype), S->nrows, S->ncols);
+    MatrixOwner Tm(matrix_new(type_of_code(ctype), S->nrows, S->ncols));
     if (S->nvals == 0) return Tm;
-    try {
-        const int code = op->op, stype = S->type->code;
-        const int64_t m = (int64_t)S->nrows, n = (int64_t)S->ncols, nnz = S->nvals;
-        const size_t ssize = S->type->size, csize = type_size(ctype);
-        const int64_t k = sel_is_value(code) ? 0 : thunk_as<int64_t>(th);
-        const bool t_iso = S->iso && !full_values;
-        const int a_iso = S->iso ? 1 : 0;
-        const int trivial = sel_trivial(code, m, n, k);
-        if (trivial < 0) return Tm;
+    const int code = op->op, stype = S->type->code;
+    const int64_t m = (int64_t)S->nrows, n = (int64_t)S->ncols, nnz = S->nvals;
+    const size_t ssize = S->type->size;
+    const int64_t k = sel_is_value(code) ? 0 : thunk_as<int64_t>(th);
+    const bool t_iso = S->iso && !full_values;
+    const int a_iso = S->iso ? 1 : 0;
+    const int trivial = sel_trivial(code, m, n, k);
+    if (trivial < 0) return Tm;
+    // the output: row pointers, columns, and the kept values (one when t_iso) moved in S's type; matrix_adopt casts them to C's type
+    DevPtr<int64_t> Tp;
+    DevPtr<int32_t> Tj;
+    DevPtr<char> raw;
+    auto alloc_out = [&](int64_t kept) {
+        Tp.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1)));
+        Tj.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)kept));
+        raw.reset((char *)dev_alloc(ssize * (size_t)(t_iso ? 1 : kept)));
+        if (t_iso) d2d(raw.p, S->d_val, ssize);
+    };
 
-        // the kept entries' values: moved in S's type, cast to C's type afterwards when the two differ
-        auto finish_values = [&](void *raw, int64_t kept) {  // raw: kept values (1 when t_iso) of S's type; takes ownership
-            DevPtr<char> own((char *)raw);
-            const int64_t nv = t_iso ? 1 : kept;
-            if (stype == ctype) Tm->d_val = own.release();
-            else {
-                Tm->d_val = dev_alloc(csize * (size_t)nv);
-                cast_array(ctype, Tm->d_val, stype, own.p, nv);
-            }
-            Tm->iso = t_iso;
-            Tm->nvals = kept;
-        };
-
-        if (trivial > 0 || code == SEL_ROWLE || code == SEL_ROWGT) {
-            // a contiguous range [lo, hi) of entries: slice the row pointers, copy columns and values
-            int64_t lo = 0, hi = nnz;
-            if (trivial == 0) {
-                int64_t cut = 0;
-                d2h(&cut, S->d_ptr + (k + 1), sizeof(int64_t));  // (0 <= k < m - 1 here)
-                if (code == SEL_ROWLE) hi = cut;
-                else lo = cut;
-            }
-            const int64_t kept = hi - lo;
-            if (kept == 0) return Tm;
-            Tm->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1));
-            if (trivial > 0) d2d(Tm->d_ptr, S->d_ptr, sizeof(int64_t) * (size_t)(m + 1));
-            else {
-                hipLaunchKernelGGL(k_select_rowslice, grid1(m + 1), dim3(256), 0, ctx().stream, (const int64_t *)S->d_ptr, m, lo, hi, Tm->d_ptr);
-                ctx().stats.kernel_launches += 1;
-            }
-            Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)kept);
-            d2d(Tm->d_col, S->d_col + lo, sizeof(int32_t) * (size_t)kept);
-            DevPtr<char> raw((char *)dev_alloc(ssize * (size_t)(t_iso ? 1 : kept)));
-            if (t_iso) d2d(raw.p, S->d_val, ssize);
-            else move_values(raw.p, (const char *)S->d_val + (a_iso ? 0 : ssize * (size_t)lo), a_iso, kept, ssize);
-            finish_values(raw.release(), kept);
-            GRB_HIP(hipGetLastError());
-            return Tm;
+    if (trivial > 0 || code == SEL_ROWLE || code == SEL_ROWGT) {
+        // a contiguous range [lo, hi) of entries: slice the row pointers, copy columns and values
+        int64_t lo = 0, hi = nnz;
+        if (trivial == 0) {
+            int64_t cut = 0;
+            d2h(&cut, S->d_ptr + (k + 1), sizeof(int64_t));  // (0 <= k < m - 1 here)
+            if (code == SEL_ROWLE) hi = cut;
+            else lo = cut;
         }
+        const int64_t kept = hi - lo;
+        if (kept == 0) return Tm;
+        alloc_out(kept);
+        if (trivial > 0) d2d(Tp.p, S->d_ptr, sizeof(int64_t) * (size_t)(m + 1));
+        else {
+            hipLaunchKernelGGL(k_select_rowslice, grid1d(m + 1), dim3(256), 0, ctx().stream, (const int64_t *)S->d_ptr, m, lo, hi, Tp.p);
+            ctx().stats.kernel_launches += 1;
+        }
+        d2d(Tj.p, S->d_col + lo, sizeof(int32_t) * (size_t)kept);
+        if (!t_iso) {
+            values_expanded(raw.p, (const char *)S->d_val + (a_iso ? 0 : ssize * (size_t)lo), a_iso, kept, ssize);
+            ctx().stats.kernel_launches += a_iso;
+        }
+        matrix_adopt(Tm.get(), Tp.release(), Tj.release(), raw.release(), stype, kept, t_iso);
+        GRB_HIP(hipGetLastError());
+        return Tm;
+    }
 
-        // ---- the flag / scan / rows / fill passes ----
-        const int64_t nblocks = ceil_div(nnz, 64);
-        DevBuf<unsigned long long> keep((size_t)nblocks);
-        DevBuf<int64_t> bsum((size_t)nblocks + 1);
-        const dim3 fgrid((unsigned)ceil_div(nblocks, 4 * SEL_BPW)), fblock(256);
-        const int64_t *Ap = S->d_ptr;
-        const int32_t *Aj = S->d_col;
-        if (!sel_is_value(code)) {
-            switch (code) {
+    // ---- the flag / scan / rows / fill passes ----
+    const int64_t nblocks = ceil_div(nnz, 64);
+    DevBuf<unsigned long long> keep((size_t)nblocks);
+    DevBuf<int64_t> bsum((size_t)nblocks + 1);
+    const dim3 fgrid((unsigned)ceil_div(nblocks, 4 * SEL_BPW)), fblock(256);
+    const int64_t *Ap = S->d_ptr;
+    const int32_t *Aj = S->d_col;
+    if (!sel_is_value(code)) {
+        switch (code) {
 #define SEL_CASE(OPC)                                                                                                                              \
     case OPC:                                                                                                                                      \
         hipLaunchKernelGGL((k_select_flag<OPC, char>), fgrid, fblock, 0, ctx().stream, Ap, m, Aj, (const char *)nullptr, 0, nnz, nblocks, k, (char)0, \
                            keep.p, bsum.p);                                                                                                        \
         break;
-                SEL_FOR_POS_FLAG(SEL_CASE)
+            SEL_FOR_POS_FLAG(SEL_CASE)
 #undef SEL_CASE
-            default: fail(GrB_PANIC, "select: unknown operator code");
-            }
-        } else {
-            // entry and thunk are compared in the operator's type: an operator of another type than the matrix's (A.select(">=", 2.5) on an
-            // integer matrix) costs one cast pass over the values first (11 x 11 type pairs are not instantiated per operator)
-            const int ot = op->type;
-            DevPtr<char> xcast;
-            const void *xs = S->d_val;
-            if (ot != stype) {
-                const int64_t nv = a_iso ? 1 : nnz;
-                xcast.p = (char *)dev_alloc(type_size(ot) * (size_t)nv);
-                cast_array(ot, xcast.p, stype, S->d_val, nv);
-                xs = xcast.p;
-            }
-            GRB_DISPATCH_TYPE(ot, TO, { launch_flag_value<TO>(code, fgrid, Ap, m, Aj, xs, a_iso, nnz, nblocks, thunk_as<TO>(th), keep.p, bsum.p); })
+        default: fail(GrB_PANIC, "select: unknown operator code");
         }
-        prim_exclusive_sum_i64(bsum.p, bsum.p, nblocks + 1);
-        ctx().stats.kernel_launches += 2;
-        int64_t kept = 0;
-        d2h(&kept, bsum.p + nblocks, sizeof(int64_t));
-        if (kept > 0) {
-            Tm->d_ptr = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1));
-            hipLaunchKernelGGL(k_select_rowptr, grid1(m + 1), dim3(256), 0, ctx().stream, Ap, m, nnz, nblocks, (const unsigned long long *)keep.p,
-                               (const int64_t *)bsum.p, Tm->d_ptr);
-            Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)kept);
-            void *raw = dev_alloc(ssize * (size_t)(t_iso ? 1 : kept));
-            DevPtr<char> raw_own((char *)raw);
-            if (t_iso) d2d(raw, S->d_val, ssize);
-            void *nx = t_iso ? nullptr : raw;
-#define SEL_FILL(U)                                                                                                                             \
-    hipLaunchKernelGGL((k_select_fill<U>), grid1(nnz), dim3(256), 0, ctx().stream, Aj, (const U *)S->d_val, a_iso, nnz, (const unsigned long long *)keep.p, \
-                       (const int64_t *)bsum.p, Tm->d_col, (U *)nx)
-            switch (ssize) {
-            case 1: SEL_FILL(uint8_t); break;
-            case 2: SEL_FILL(uint16_t); break;
-            case 4: SEL_FILL(uint32_t); break;
-            default: SEL_FILL(uint64_t); break;
-            }
-#undef SEL_FILL
-            ctx().stats.kernel_launches += 2;
-            finish_values(raw_own.release(), kept);
-        }
-        GRB_HIP(hipGetLastError());
-        return Tm;
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
+    } else {
+        // entry and thunk are compared in the operator's type: an operator of another type than the matrix's (A.select(">=", 2.5) on an
+        // integer matrix) costs one cast pass over the values first (11 x 11 type pairs are not instantiated per operator)
+        const int ot = op->type;
+        DevPtr<char> xcast;
+        const void *xs = values_as(S, ot, xcast);
+        GRB_DISPATCH_TYPE(ot, TO, { launch_flag_value<TO>(code, fgrid, Ap, m, Aj, xs, a_iso, nnz, nblocks, thunk_as<TO>(th), keep.p, bsum.p); })
     }
+    prim_exclusive_sum_i64(bsum.p, bsum.p, nblocks + 1);
+    ctx().stats.kernel_launches += 2;
+    int64_t kept = 0;
+    d2h(&kept, bsum.p + nblocks, sizeof(int64_t));
+    if (kept > 0) {
+        alloc_out(kept);
+        hipLaunchKernelGGL(k_select_rowptr, grid1d(m + 1), dim3(256), 0, ctx().stream, Ap, m, nnz, nblocks, (const unsigned long long *)keep.p,
+                           (const int64_t *)bsum.p, Tp.p);
+        GRB_DISPATCH_SIZE(ssize, U, hipLaunchKernelGGL((k_select_fill<U>), grid1d(nnz), dim3(256), 0, ctx().stream, Aj, (const U *)S->d_val, a_iso, nnz,
+                                                       (const unsigned long long *)keep.p, (const int64_t *)bsum.p, Tj.p, (U *)(t_iso ? nullptr : raw.p)))
+        ctx().stats.kernel_launches += 2;
+        matrix_adopt(Tm.get(), Tp.release(), Tj.release(), raw.release(), stype, kept, t_iso);
+    }
+    GRB_HIP(hipGetLastError());
+    return Tm;
 }
 
 static void check_select_op(const GB_IndexUnaryOp_opaque *op)
@@ -409,30 +357,16 @@ static void matrix_select(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_
     check_matrix(A, "A");
     if (Mask) check_matrix(Mask, "Mask");
     check_select_op(op);
-    const bool t0 = desc && desc->t0;  // (T1 is ignored: there is no second input)
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
-    const uint64_t in_rows = t0 ? A->ncols : A->nrows, in_cols = t0 ? A->nrows : A->ncols;
+    const MDesc f = mdesc_of(desc);  // (T1 is ignored: there is no second input)
+    const uint64_t in_rows = f.t0 ? A->ncols : A->nrows, in_cols = f.t0 ? A->nrows : A->ncols;
     if (C->nrows != in_rows || C->ncols != in_cols)
         fail(GrB_DIMENSION_MISMATCH, "GrB_select: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the input " +
-                                         (t0 ? "(transposed) " : "") + std::to_string(in_rows) + " x " + std::to_string(in_cols));
-    if (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "GrB_select: mask shape does not match the output");
-    if (accum && (accum->type != C->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_select: accum operator type must equal the output type");
-    if (!Mask && comp) {  // complement of "no mask": nothing may be written
-        if (replace) matrix_release_storage(C);
-        return;
-    }
+                                         (f.t0 ? "(transposed) " : "") + std::to_string(in_rows) + " x " + std::to_string(in_cols));
+    check_mask_accum("GrB_select", C, Mask, accum);
+    if (matrix_writes_nothing(C, Mask, f)) return;
     ctx().stats = GrX_Stats{};
-    GB_Matrix_opaque *S = t0 ? matrix_transpose_cached(A) : A;
-    // T is a fresh object, so C may alias A or the mask
-    GB_Matrix_opaque *Tm = select_build(S, op, th, C->type->code, Mask || accum);
-    try {
-        if (C == A) matrix_invalidate_caches(C);
-        matrix_apply_write_rule(C, Mask, accum, Tm, replace, comp, structure);
-    } catch (...) {
-        matrix_free(Tm);
-        throw;
-    }
-    matrix_free(Tm);
+    GB_Matrix_opaque *S = f.t0 ? matrix_transpose_cached(A) : A;
+    matrix_finish(C, Mask, accum, select_build(S, op, th, C->type->code, Mask || accum), f, C == A);
     ctx().stats.out_nvals = C->nvals;
     if (ctx().blocking) sync_stream();
 }
@@ -481,7 +415,7 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
         switch (code) {
 #define SEL_CASE(OPC)                                                                                                                       \
     case OPC:                                                                                                                               \
-        hipLaunchKernelGGL((k_vselect<OPC, char>), grid1(threads), dim3(256), 0, ctx().stream, n, (const char *)nullptr, (const uint64_t *)u->d_bits, k, \
+        hipLaunchKernelGGL((k_vselect<OPC, char>), grid1d(threads), dim3(256), 0, ctx().stream, n, (const char *)nullptr, (const uint64_t *)u->d_bits, k, \
                            (char)0, t_bits.p);                                                                                              \
         break;
             SEL_FOR_POS(SEL_CASE)
@@ -497,7 +431,7 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
             cast_array(ot, xcast.p, u->type->code, u->d_val, n);
             xs = xcast.p;
         }
-        GRB_DISPATCH_TYPE(ot, TO, { launch_vselect_value<TO>(code, grid1(threads), n, xs, (const uint64_t *)u->d_bits, thunk_as<TO>(th), t_bits.p); })
+        GRB_DISPATCH_TYPE(ot, TO, { launch_vselect_value<TO>(code, grid1d(threads), n, xs, (const uint64_t *)u->d_bits, thunk_as<TO>(th), t_bits.p); })
         ctx().stats.kernel_launches += 1;
     }
     // t's values in w's type (a buffer of its own when w is u: the write rule works in place)
