@@ -299,7 +299,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)) */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C) */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */

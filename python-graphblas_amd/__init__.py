@@ -14,7 +14,7 @@ syntax ``C(mask, accum, replace) << A.mxm(B, semiring)`` documented at
 from . import _lib, descriptor, dtypes, exceptions
 from .base import _replace_singleton as replace
 from .base import record_calls
-from .operators import agg, binary, indexunary, monoid, op, select, semiring
+from .operators import agg, binary, indexunary, monoid, op, select, semiring, unary
 
 _initialized = False
 backend = "mi355x"
@@ -46,4 +46,4 @@ from .matrix import Matrix, TransposedMatrix  # noqa: E402
 from .vector import Vector  # noqa: E402
 from .base import Scalar  # noqa: E402
 
-__all__ = ["init", "MAX_SIZE", "Matrix", "Vector", "Scalar", "semiring", "binary", "monoid", "op", "agg", "select", "indexunary", "dtypes", "replace", "exceptions"]
+__all__ = ["init", "MAX_SIZE", "Matrix", "Vector", "Scalar", "semiring", "binary", "monoid", "op", "agg", "select", "indexunary", "unary", "dtypes", "replace", "exceptions"]

@@ -122,9 +122,16 @@ def _declare(L):
         getattr(L, f"GrB_Scalar_setElement_{t}").argtypes = [c_void_p, ct]
         for kind in ("Matrix", "Vector"):  # (C, Mask, accum, op, A, y, desc)
             getattr(L, f"GrB_{kind}_select_{t}").argtypes = [c_void_p] * 5 + [ct, c_void_p]
+            getattr(L, f"GrB_{kind}_apply_BinaryOp1st_{t}").argtypes = [c_void_p] * 4 + [ct, c_void_p, c_void_p]  # (C, Mask, accum, op, x, A, desc)
+            getattr(L, f"GrB_{kind}_apply_BinaryOp2nd_{t}").argtypes = [c_void_p] * 5 + [ct, c_void_p]
+            getattr(L, f"GrB_{kind}_apply_IndexOp_{t}").argtypes = [c_void_p] * 5 + [ct, c_void_p]
     L.GrB_Vector_resize.argtypes = [c_void_p, c_u64]
     L.GrB_Matrix_select_Scalar.argtypes = [c_void_p] * 7
     L.GrB_Vector_select_Scalar.argtypes = [c_void_p] * 7
+    for kind in ("Matrix", "Vector"):
+        getattr(L, f"GrB_{kind}_apply").argtypes = [c_void_p] * 6
+        for form in ("BinaryOp1st", "BinaryOp2nd", "IndexOp"):
+            getattr(L, f"GrB_{kind}_apply_{form}_Scalar").argtypes = [c_void_p] * 7
     L.GrB_Scalar_new.argtypes = [P(c_void_p), c_void_p]
     L.GrB_Scalar_free.argtypes = [P(c_void_p)]
     for t in TYPE_NAMES:

@@ -499,6 +499,21 @@ class GrBScalarArg:
                 pass
 
 
+def _scalar_carg(value, what):
+    """A scalar argument of a select / apply call: (its dtype, what is handed to C, the entry point's suffix).  A :class:`Scalar` goes
+    through the ``_Scalar`` form, a Python or numpy number through the typed form of its own dtype."""
+    if isinstance(value, Scalar):
+        return value.dtype, GrBScalarArg(value), "Scalar"
+    if isinstance(value, (bool, np.bool_)):
+        return BOOL, bool(value), "BOOL"
+    if isinstance(value, (int, float, np.integer, np.floating)):
+        dtype = lookup_dtype(np.int64 if isinstance(value, int) else (np.float64 if isinstance(value, float) else np.asarray(value).dtype))
+        if isinstance(value, int) and not -(1 << 63) <= value < (1 << 63):
+            dtype = lookup_dtype(np.uint64)
+        return dtype, dtype.np_type.type(value).item(), dtype.name
+    raise TypeError(f"{what}: {type(value).__name__}; expected a number or a Scalar")
+
+
 def select_expression(x, op, thunk, *, output_type, shape, at=False):
     """``x.select(op, thunk)`` for a Matrix / TransposedMatrix / Vector ``x`` (reference core/matrix.py:2597-2623, core/vector.py select):
     the delayed call of ``GrB_<kind>_select_<thunk dtype>``, or of the ``_Scalar`` form for a :class:`Scalar` thunk."""
@@ -513,17 +528,7 @@ def select_expression(x, op, thunk, *, output_type, shape, at=False):
         return MaskSelect(base, op)
     if thunk is None:
         thunk = False  # (the reference's default, core/matrix.py:2616)
-    if isinstance(thunk, Scalar):
-        tdtype, carg, suffix = thunk.dtype, GrBScalarArg(thunk), "Scalar"
-    elif isinstance(thunk, (bool, np.bool_)):
-        tdtype, carg, suffix = BOOL, bool(thunk), "BOOL"
-    elif isinstance(thunk, (int, float, np.integer, np.floating)):
-        tdtype = lookup_dtype(np.int64 if isinstance(thunk, int) else (np.float64 if isinstance(thunk, float) else np.asarray(thunk).dtype))
-        if isinstance(thunk, int) and not -(1 << 63) <= thunk < (1 << 63):
-            tdtype = lookup_dtype(np.uint64)
-        carg, suffix = tdtype.np_type.type(thunk).item(), tdtype.name
-    else:
-        raise TypeError(f"Bad type for argument `thunk` in {kind}.select(...): {type(thunk).__name__}; expected a number or a Scalar")
+    tdtype, carg, suffix = _scalar_carg(thunk, f"Bad type for argument `thunk` in {kind}.select(...)")
     top = get_typed_op(op, base.dtype, tdtype, kind="select")
     return Expression("select", f"GrB_{kind}_select_{suffix}", [base, carg], op=top, output_type=output_type, shape=shape, at=at,
                       dtype=base.dtype)
@@ -555,3 +560,59 @@ class _Replace:
 
 
 _replace_singleton = _Replace()
+
+
+_APPLY_USAGE = ("apply only accepts UnaryOp with no scalars or BinaryOp with `left` or `right` scalar or IndexUnaryOp with `right` "
+                "thunk.")
+
+
+def apply_expression(x, op, right=None, left=None, *, output_type, shape, at=False):
+    """``x.apply(op, right=None, *, left=None)`` for a Matrix / TransposedMatrix / Vector ``x`` (reference core/matrix.py apply,
+    core/vector.py apply): the delayed call of ``GrB_<kind>_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp_<scalar dtype>`` (the
+    ``_Scalar`` forms for a :class:`Scalar`), or of the unary ``GrB_<kind>_apply``, which the library does not implement."""
+    from .operators import IndexOp, _OpBase, _from_string, select as _select
+
+    base = x._matrix if hasattr(x, "_matrix") else x
+    kind = base._grb_kind
+    for name, value in (("left", left), ("right", right)):
+        if isinstance(value, (BaseType, Mask, Expression)) or hasattr(value, "_matrix"):
+            raise TypeError(f"Bad type for argument `{name}` in {kind}.apply(...): {type(value).__name__}; expected a number or a Scalar")
+    if isinstance(op, str):
+        s = op.strip().lower()
+        if hasattr(_select, s) and isinstance(getattr(_select, s), IndexOp):
+            op = getattr(_select, s)
+        else:
+            try:  # a binary operator where a scalar is bound, else an index-unary spelling ("tril", "row<=", ...)
+                op = _from_string(op, "binary") if (left is not None or right is not None) else _from_string(op, "select")
+            except ValueError:
+                op = _from_string(op, "select")
+    opclass = op.opclass if isinstance(op, (TypedOp, _OpBase)) else None
+    if opclass == "UnaryOp":
+        if left is not None or right is not None:
+            raise TypeError(_APPLY_USAGE)
+        top = op if isinstance(op, TypedOp) else op[base.dtype]
+        return Expression("apply", f"GrB_{kind}_apply", [base], op=top, output_type=output_type, shape=shape, at=at, dtype=base.dtype)
+    if opclass in ("SelectOp", "IndexUnaryOp"):
+        if left is not None:
+            raise TypeError("Do not use `left` with an IndexUnaryOp: its thunk is `right`")
+        tdtype, carg, suffix = _scalar_carg(False if right is None else right, f"Bad type for argument `right` in {kind}.apply(...)")
+        if opclass == "IndexUnaryOp":  # rowindex / colindex / diagindex: the operator's own type, INT64 unless asked for otherwise
+            top = op if isinstance(op, TypedOp) else op[lookup_dtype("INT64")]
+        else:
+            top = get_typed_op(op, base.dtype, tdtype, kind="select")
+        return Expression("apply", f"GrB_{kind}_apply_IndexOp_{suffix}", [base, carg], op=top, output_type=output_type, shape=shape, at=at,
+                          dtype=top.return_type)
+    if opclass in ("BinaryOp", "Monoid"):
+        if left is not None and right is not None:
+            raise TypeError("Cannot provide both `left` and `right` to apply")
+        if left is None and right is None:
+            raise TypeError(_APPLY_USAGE)
+        first = left is not None
+        sdtype, carg, suffix = _scalar_carg(left if first else right, f"Bad type for argument `{'left' if first else 'right'}` in {kind}.apply(...)")
+        top = get_typed_op(op, base.dtype, sdtype, kind="binary")
+        if top.opclass == "Monoid":  # (a monoid in place of a binary operator means its binary operator)
+            top = top.binaryop
+        args = [carg, base] if first else [base, carg]
+        return Expression("apply", f"GrB_{kind}_apply_BinaryOp{'1st' if first else '2nd'}_{suffix}", args, op=top, output_type=output_type,
+                          shape=shape, at=at, dtype=top.return_type)
+    raise TypeError(_APPLY_USAGE)

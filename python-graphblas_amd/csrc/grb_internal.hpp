@@ -39,13 +39,16 @@ enum OpCode : int {
 inline bool op_is_comparison(int op) { return op >= OP_EQ && op <= OP_LE; }
 
 // the builtin index-unary operators that return BOOL (GrB_select; grb_select.hip) have a code space of their own, above OP_UNSUPPORTED:
-// canonical_op rejects them wherever a binary operator is expected.  ROWINDEX / COLINDEX / DIAGINDEX (apply operators) stay OP_UNSUPPORTED
+// canonical_op rejects them wherever a binary operator is expected.
 enum SelOp : int {
     SEL_TRIL = 2000, SEL_TRIU, SEL_DIAG, SEL_OFFDIAG, SEL_COLLE, SEL_COLGT, SEL_ROWLE, SEL_ROWGT,
     SEL_VALUEEQ, SEL_VALUENE, SEL_VALUEGT, SEL_VALUEGE, SEL_VALUELT, SEL_VALUELE
 };
 inline bool op_is_select(int op) { return op >= SEL_TRIL && op <= SEL_VALUELE; }
 inline bool sel_is_value(int op) { return op >= SEL_VALUEEQ && op <= SEL_VALUELE; }
+// ... and the ones that return an index (GrB_apply alone; grb_apply.hip) the range beside it: GrB_select rejects them (check_select_op)
+enum ApplyOp : int { APPLY_ROWINDEX = 3000, APPLY_COLINDEX, APPLY_DIAGINDEX };
+inline bool op_is_apply_index(int op) { return op >= APPLY_ROWINDEX && op <= APPLY_DIAGINDEX; }
 constexpr uint64_t MAGIC_SCALAR = 0x4752425343414c52ULL;  // "GRBSCALR"
 
 constexpr uint64_t MAGIC_VECTOR = 0x4752425645435452ULL;  // "GRBVECTR"
@@ -203,6 +206,7 @@ void preload_object();
 void preload_prim();
 void preload_select();
 void preload_extract();
+void preload_apply();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)
@@ -268,8 +272,8 @@ struct GB_Semiring_opaque {
     const char *name;
 };
 struct GB_IndexUnaryOp_opaque {
-    int op;    // SelOp, or OP_UNSUPPORTED
-    int type;  // the type entry and thunk are compared in (value operators); INT64 for the positional ones
+    int op;    // SelOp or ApplyOp
+    int type;  // the type entry and thunk are compared in (value operators); INT64 for the positional ones; the result type of ROWINDEX / COLINDEX / DIAGINDEX
     const char *name;
 };
 struct GB_Scalar_opaque {  // host side: a value + presence (grb_surface.hip)

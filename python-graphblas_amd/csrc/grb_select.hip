@@ -18,67 +18,11 @@
 // that keeps everything or nothing is decided on the host.
 #include <algorithm>
 
-#include "grb_internal.hpp"
-#include "grb_ops.hpp"
+#include "grb_index_ops.hpp"  // Thunk, sel_pos / sel_val, the entry -> row walk (shared with grb_apply.hip)
 
 namespace grb {
 
-struct Thunk {  // the scalar y of a select call: its type and its bytes
-    int type;
-    unsigned char v[8];
-};
-template <typename X> static Thunk thunk_of(int type, X x)
-{
-    Thunk t{type, {0}};
-    memcpy(t.v, &x, sizeof(X));
-    return t;
-}
-template <typename D> static D thunk_as(const Thunk &t)
-{
-    D out{};
-    GRB_DISPATCH_TYPE(t.type, TY, {
-        TY y;
-        memcpy(&y, t.v, sizeof(TY));
-        out = cast_value<D, TY>(y);
-    })
-    return out;
-}
-
-template <int OP> GRB_HD bool sel_pos(int64_t i, int64_t j, int64_t k)
-{
-    switch (OP) {
-    case SEL_TRIL: return j <= i + k;
-    case SEL_TRIU: return j >= i + k;
-    case SEL_DIAG: return j == i + k;
-    case SEL_OFFDIAG: return j != i + k;
-    case SEL_COLLE: return j <= k;
-    case SEL_COLGT: return j > k;
-    case SEL_ROWLE: return i <= k;
-    default: return i > k;
-    }
-}
-template <int OP, typename T> GRB_HD bool sel_val(T a, T y)
-{
-    switch (OP) {
-    case SEL_VALUEEQ: return a == y;
-    case SEL_VALUENE: return a != y;
-    case SEL_VALUEGT: return a > y;
-    case SEL_VALUEGE: return a >= y;
-    case SEL_VALUELT: return a < y;
-    default: return a <= y;
-    }
-}
 constexpr bool sel_needs_row(int op) { return op == SEL_TRIL || op == SEL_TRIU || op == SEL_DIAG || op == SEL_OFFDIAG; }
-
-// the lanes of ONE wavefront exchange data through LDS (the same three steps as mw_sync of grb_mxm.hip)
-__device__ __forceinline__ void sel_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-constexpr int SEL_BPW = 8;  // blocks of 64 entries a wavefront walks: one search in d_ptr per 512 entries
 
 // ---- 1. flag pass ------------------------------------------------------------------------------------------------------
 // keep[b] bit l = entry 64 b + l stays; bsum[b] = popc(keep[b]); bsum[nblocks] = 0 (the scan turns it into the total)
@@ -96,40 +40,13 @@ __global__ void __launch_bounds__(256) k_select_flag(const int64_t *__restrict__
     if (blockIdx.x == 0 && threadIdx.x == 0) bsum[nblocks] = 0;
     int64_t r = 0;  // (wave-uniform) the row of the first entry of the current block
     if constexpr (NEED_ROW) {
-        if (b0 < b1) {  // Ap[r] <= 64 b0 < Ap[r + 1]: Ap[0] = 0 and Ap[m] = nnz bracket every entry
-            const int64_t p0 = b0 << 6;
-            int64_t lo = 0, hi = m;
-            while (hi - lo > 1) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (Ap[mid] <= p0) lo = mid;
-                else hi = mid;
-            }
-            r = lo;
-        }
+        if (b0 < b1) r = walk_first_row(Ap, m, b0 << 6);
     }
     for (int64_t b = b0; b < b1; b++) {
         const int64_t p = b << 6, e = p + lane;
         const bool active = e < nnz;
         int64_t row = r;
-        if constexpr (NEED_ROW) {
-            // row of entry e = r + #{rows r' >= r whose end Ap[r' + 1] <= e}: 64 row ends at a time, counted by a search in LDS
-            const int64_t e_last = p + 63 < nnz ? p + 63 : nnz - 1;
-            for (int64_t base = r + 1;; base += 64) {
-                const int64_t idx = base + lane;
-                s_end[wave][lane] = idx <= m ? Ap[idx] : INT64_MAX;
-                sel_sync();
-                int c = 0;
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1)
-                    if (s_end[wave][c + step - 1] <= e) c += step;
-                if (c == 63 && s_end[wave][63] <= e) c = 64;
-                row += c;
-                const int64_t last = s_end[wave][63];
-                sel_sync();
-                if (last > e_last) break;
-            }
-            r = __shfl(row, 63);  // (the next block walks on from the row of this block's last entry)
-        }
+        if constexpr (NEED_ROW) row = walk_block_rows(Ap, m, nnz, p, lane, s_end[wave], r);
         bool pred = false;
         if (active) {
             if constexpr (IS_VALUE) pred = sel_val<OP, T>(Ax[a_iso ? 0 : e], y);
@@ -450,16 +367,6 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
     if (ctx().blocking) sync_stream();
 }
 
-static Thunk thunk_of_scalar(const GB_Scalar_opaque *y)
-{
-    if (!y) fail(GrB_NULL_POINTER, "GrB_select: the thunk scalar is NULL");
-    if (y->magic != MAGIC_SCALAR) fail(y->magic == MAGIC_FREED ? GrB_UNINITIALIZED_OBJECT : GrB_INVALID_OBJECT, "GrB_select: the thunk is not a valid GrB_Scalar");
-    if (!y->has) fail(GrB_EMPTY_OBJECT, "GrB_select: the thunk scalar is empty");
-    Thunk t{y->type->code, {0}};
-    memcpy(t.v, y->value, sizeof(t.v));
-    return t;
-}
-
 void preload_select() { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_select_rowptr)); (void)hipGetLastError(); }
 
 }  // namespace grb
@@ -471,7 +378,7 @@ extern "C" GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask
 {
     GRB_TRY
     check_matrix(C, "C");
-    matrix_select(C, Mask, accum, op, A, thunk_of_scalar(y), desc);
+    matrix_select(C, Mask, accum, op, A, thunk_of_scalar(y, "GrB_select"), desc);
     GRB_CATCH(errp(C))
 }
 extern "C" GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_IndexUnaryOp op,
@@ -479,7 +386,7 @@ extern "C" GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask
 {
     GRB_TRY
     check_vector_any(w, "w");
-    vector_select(w, mask, accum, op, u, thunk_of_scalar(y), desc);
+    vector_select(w, mask, accum, op, u, thunk_of_scalar(y, "GrB_select"), desc);
     GRB_CATCH(errp(w))
 }
 

@@ -6,11 +6,13 @@
 //   * builtin unary, index-unary and the remaining binary operators as DATA symbols.  The kernels implement none of the unary and
 //     extra binary ones: every entry point that consumes an operator goes through canonical_op(), which rejects their codes with
 //     GrB_NOT_IMPLEMENTED.  The index-unary operators that return BOOL (GrB_TRIL ... GrB_ROWGT, GrB_VALUE*_<T>) carry the SelOp
-//     codes GrB_select runs on (grb_select.hip); GrB_ROWINDEX / COLINDEX / DIAGINDEX_* are apply operators and stay handle-only;
+//     codes GrB_select runs on (grb_select.hip); GrB_ROWINDEX / COLINDEX / DIAGINDEX_* carry the ApplyOp codes of GrB_apply (grb_apply.hip);
 //   * GrB_Scalar for real (a host-side value + presence: the reference passes scalars by GrB_Scalar handle in C API 2.0 calls);
 //   * the entry points of the operations this library does not accelerate, with their C API 2.0 signatures, returning
 //     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip;
-//     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip.)
+//     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip;
+//     GrB_{Matrix,Vector}_apply_{BinaryOp1st,BinaryOp2nd,IndexOp}_{<T>,Scalar}: grb_apply.hip.  The unary GrB_Matrix_apply /
+//     GrB_Vector_apply stay here: no kernel implements a unary operator.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -69,12 +71,12 @@ DEF_UNOP(GrB_BNOT_UINT8, UINT8)
 DEF_UNOP(GrB_BNOT_UINT16, UINT16)
 DEF_UNOP(GrB_BNOT_UINT32, UINT32)
 DEF_UNOP(GrB_BNOT_UINT64, UINT64)
-DEF_IDXOP(GrB_ROWINDEX_INT32, OP_UNSUPPORTED, INT32)
-DEF_IDXOP(GrB_ROWINDEX_INT64, OP_UNSUPPORTED, INT64)
-DEF_IDXOP(GrB_COLINDEX_INT32, OP_UNSUPPORTED, INT32)
-DEF_IDXOP(GrB_COLINDEX_INT64, OP_UNSUPPORTED, INT64)
-DEF_IDXOP(GrB_DIAGINDEX_INT32, OP_UNSUPPORTED, INT32)
-DEF_IDXOP(GrB_DIAGINDEX_INT64, OP_UNSUPPORTED, INT64)
+DEF_IDXOP(GrB_ROWINDEX_INT32, APPLY_ROWINDEX, INT32)
+DEF_IDXOP(GrB_ROWINDEX_INT64, APPLY_ROWINDEX, INT64)
+DEF_IDXOP(GrB_COLINDEX_INT32, APPLY_COLINDEX, INT32)
+DEF_IDXOP(GrB_COLINDEX_INT64, APPLY_COLINDEX, INT64)
+DEF_IDXOP(GrB_DIAGINDEX_INT32, APPLY_DIAGINDEX, INT32)
+DEF_IDXOP(GrB_DIAGINDEX_INT64, APPLY_DIAGINDEX, INT64)
 DEF_IDXOP(GrB_TRIL, SEL_TRIL, INT64)
 DEF_IDXOP(GrB_TRIU, SEL_TRIU, INT64)
 DEF_IDXOP(GrB_DIAG, SEL_DIAG, INT64)
@@ -301,12 +303,6 @@ NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB
 NI_M(GrB_Matrix_removeElement, GrB_Index, GrB_Index)
 NI_M(GrB_Matrix_assign_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_Scalar, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
 NI_M(GrB_Matrix_setElement_Scalar, const GrB_Scalar, GrB_Index, GrB_Index)
-NI_V(GrB_Vector_apply_BinaryOp1st_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Scalar, const GrB_Vector, const GrB_Descriptor)
-NI_V(GrB_Vector_apply_BinaryOp2nd_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, const GrB_Scalar, const GrB_Descriptor)
-NI_V(GrB_Vector_apply_IndexOp_Scalar, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, const GrB_Scalar, const GrB_Descriptor)
-NI_M(GrB_Matrix_apply_BinaryOp1st_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Scalar, const GrB_Matrix, const GrB_Descriptor)
-NI_M(GrB_Matrix_apply_BinaryOp2nd_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Scalar, const GrB_Descriptor)
-NI_M(GrB_Matrix_apply_IndexOp_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Matrix, const GrB_Scalar, const GrB_Descriptor)
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Vector, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
@@ -335,12 +331,6 @@ extern "C" GrB_Info GrB_Semiring_new(GrB_Semiring *, GrB_Monoid, GrB_BinaryOp) {
     extern "C" GrB_Info GrB_Monoid_new_##NAME(GrB_Monoid *, GrB_BinaryOp, ctype) { return GrB_NOT_IMPLEMENTED; }                     \
     NI_M(GrB_Matrix_setElement_##NAME, ctype, GrB_Index, GrB_Index)                                                                  \
     extern "C" GrB_Info GrB_Matrix_reduce_##NAME(ctype *, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; } \
-    NI_M(GrB_Matrix_assign_##NAME, const GrB_Matrix, const GrB_BinaryOp, ctype, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor) \
-    NI_V(GrB_Vector_apply_BinaryOp1st_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, ctype, const GrB_Vector, const GrB_Descriptor) \
-    NI_V(GrB_Vector_apply_BinaryOp2nd_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, ctype, const GrB_Descriptor) \
-    NI_V(GrB_Vector_apply_IndexOp_##NAME, const GrB_Vector, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Vector, ctype, const GrB_Descriptor) \
-    NI_M(GrB_Matrix_apply_BinaryOp1st_##NAME, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, ctype, const GrB_Matrix, const GrB_Descriptor) \
-    NI_M(GrB_Matrix_apply_BinaryOp2nd_##NAME, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, ctype, const GrB_Descriptor) \
-    NI_M(GrB_Matrix_apply_IndexOp_##NAME, const GrB_Matrix, const GrB_BinaryOp, const GrB_IndexUnaryOp, const GrB_Matrix, ctype, const GrB_Descriptor)
+    NI_M(GrB_Matrix_assign_##NAME, const GrB_Matrix, const GrB_BinaryOp, ctype, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
 GRB_FOR_EACH_TYPE(DEF_SURFACE_TYPED)
 #undef DEF_SURFACE_TYPED

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .base import BaseType, Expression, InfixMatMul, Mask, ScalarExpression, call, call_on, select_expression
+from .base import BaseType, Expression, InfixMatMul, Mask, ScalarExpression, apply_expression, call, call_on, select_expression
 from .dtypes import lookup_dtype
 from .exceptions import DimensionMismatch
 from .operators import binary as _binary, get_typed_op, monoid as _monoid, semiring as _semiring
@@ -350,6 +350,13 @@ class Matrix(BaseType):
         mask) keeps (reference core/matrix.py:2597-2623 -> C ``GrB_Matrix_select_<T>``)."""
         return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape)
 
+    def apply(self, op, right=None, *, left=None):
+        """``C << A.apply(binary.times, right=0.85)`` / ``A.apply(binary.minus, left=8)`` / ``A.apply(indexunary.rowindex)``: the operator
+        applied to every entry, with the scalar bound as its second (``right``) or first (``left``) argument, or -- an index-unary
+        operator -- ``right`` as its thunk (reference core/matrix.py apply -> C ``GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd /
+        _IndexOp_<T>``)."""
+        return apply_expression(self, op, right, left, output_type=Matrix, shape=self.shape)
+
     def __getitem__(self, keys):
         """``A[I, J]`` -> matrix expression, ``A[i, J]`` / ``A[I, j]`` -> vector expression, ``A[i, j]`` -> scalar expression
         (reference core/matrix.py:3020-3090 -> ``GrB_Matrix_extract`` / ``GrB_Col_extract`` / ``GrB_Matrix_extractElement_<T>``)."""
@@ -410,6 +417,10 @@ class TransposedMatrix:
     def select(self, op, thunk=None):
         """``A.T.select(op, thunk)``: the selection runs on the transpose (descriptor T0)."""
         return select_expression(self, op, thunk, output_type=Matrix, shape=self.shape, at=True)
+
+    def apply(self, op, right=None, *, left=None):
+        """``A.T.apply(op, right)``: the operator runs on the transpose (descriptor T0)."""
+        return apply_expression(self, op, right, left, output_type=Matrix, shape=self.shape, at=True)
 
     def __getitem__(self, keys):
         """``A.T[I, J]``: the same expressions with the roles of rows and columns swapped (descriptor T0)."""

@@ -13,6 +13,8 @@ here; user-defined functions, UDTs, composite aggregators and positional ops nee
 ``select`` (alias ``indexunary`` for the same names) holds the builtin index-unary operators that return BOOL -- ``tril, triu, diag,
 offdiag, rowle, rowgt, colle, colgt, indexle, indexgt, valueeq, valuene, valuegt, valuege, valuelt, valuele`` -- for
 ``A.select(op, thunk)`` (reference core/operator/select.py, indexunary.py; string spellings core/operator/utils.py:329-342).
+The same namespace holds the index-unary operators that return an index -- ``rowindex, colindex, diagindex, index`` -- for
+``A.apply(op, thunk)``; ``unary`` holds the builtin unary operators as handles only.
 """
 from __future__ import annotations
 
@@ -231,6 +233,49 @@ class SelectOp(_OpBase):
         return x.select(self, thunk)
 
 
+_APPLY_INDEX = {"rowindex": "ROWINDEX", "colindex": "COLINDEX", "diagindex": "DIAGINDEX", "index": "ROWINDEX"}  # a vector is a column: index = row
+
+
+class IndexOp(SelectOp):
+    """A builtin index-unary operator that returns an index -- ``rowindex`` (i + thunk), ``colindex`` (j + thunk), ``diagindex``
+    (j - i + thunk), ``index`` (the vector spelling of ``rowindex``) -- for ``A.apply(op, thunk)``.  It exists for INT32 and INT64 and
+    is INT64 unless asked for otherwise (``indexunary.rowindex["INT32"]``); its result has the operator's own type."""
+
+    opclass = "IndexUnaryOp"
+    positional = True
+
+    def _coerce(self, dtype):
+        return dtype if dtype.name == "INT32" else _INT64
+
+    def _gb_candidates(self, dtype):
+        return [f"GrB_{_APPLY_INDEX[self.name]}_{dtype.name}"]
+
+    def __getitem__(self, dtype):
+        t = super().__getitem__(dtype)
+        t.return_type = t.type
+        return t
+
+    def __call__(self, x, thunk=None):
+        """Functional form: ``indexunary.rowindex(A)`` / ``indexunary.colindex(A, thunk=2)``."""
+        if not hasattr(x, "apply"):
+            raise TypeError(f"Expected a Matrix or a Vector, got {type(x).__name__}")
+        return x.apply(self, thunk)
+
+
+_UNARY_NAMES = {"identity": "IDENTITY", "ainv": "AINV", "minv": "MINV", "abs": "ABS", "one": "ONE", "lnot": "LNOT"}
+
+
+class UnaryOp(_OpBase):
+    """A builtin unary operator: a handle only.  No kernel implements one, so ``A.apply(unary.ainv)`` reaches ``GrB_Matrix_apply`` and
+    raises the library's not-implemented error."""
+
+    opclass = "UnaryOp"
+
+    def _gb_candidates(self, dtype):
+        n = _UNARY_NAMES[self.name]
+        return [f"GrB_{n}_{dtype.name}", f"GxB_{n}_{dtype.name}"]
+
+
 class _Namespace:
     def __init__(self, kind):
         self._kind = kind
@@ -246,6 +291,7 @@ op = _Namespace("op")
 agg = _Namespace("agg")
 select = _Namespace("select")
 indexunary = select  # (the same operator objects under the reference's other name for them)
+unary = _Namespace("unary")
 
 for _n in _BINARY_NAMES:
     setattr(binary, _n, BinaryOp(_n))
@@ -265,6 +311,11 @@ from .dtypes import INT64 as _INT64  # noqa: E402
 
 for _n in [*_SELECT_POSITIONAL, *_SELECT_VALUE]:
     setattr(select, _n, SelectOp(_n))
+
+for _n in _APPLY_INDEX:
+    setattr(select, _n, IndexOp(_n))
+for _n in _UNARY_NAMES:
+    setattr(unary, _n, UnaryOp(_n))
 
 for _a, _m in [("sum", "plus"), ("prod", "times"), ("all", "land"), ("any", "lor"), ("min", "min"), ("max", "max"),
                ("any_value", "any")]:

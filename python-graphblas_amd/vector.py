@@ -369,6 +369,14 @@ class Vector(BaseType):
 
         return select_expression(self, op, thunk, output_type=Vector, shape=(self._size,))
 
+    def apply(self, op, right=None, *, left=None):
+        """``w << v.apply(binary.gt, right=1)`` / ``v.apply(binary.minus, left=2)`` / ``v.apply(indexunary.index)`` (reference
+        core/vector.py apply -> C ``GrB_Vector_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp_<T>``).  A vector is a column: its index is
+        the row."""
+        from .base import apply_expression
+
+        return apply_expression(self, op, right, left, output_type=Vector, shape=(self._size,))
+
     # ---- the hot path ---------------------------------------------------------------------------------------
     def vxm(self, other, op=_semiring.plus_times):
         """``w << u.vxm(A, semiring)``  (reference core/vector.py:1309-1378 -> C ``GrB_vxm``)."""
