@@ -299,7 +299,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C) */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C) */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */
@@ -496,6 +496,18 @@ GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_BinaryOp, GrB_BinaryOp)
 GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_Monoid, GrB_Monoid)
 GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)
 #undef GRB_DECL_MAT_BINARY
+/* GrB_assign (C API 2.0 section 4.3.7; grb_assign.hip): Z = C; Z(I, J) = accum ? accum(C(I, J), A) : A -- without an
+ * accumulator the positions of I x J that A leaves empty lose their entry --, then C<Mask, replace> = Z over the whole of C (the mask has C's
+ * shape; this is not GxB_subassign).  T0 transposes A; A is cast to C's type; C may alias A or the mask; every check runs before C changes.
+ * An index outside C is GrB_INDEX_OUT_OF_BOUNDS.  An index that appears TWICE in I or in J -- undefined in the specification, where the
+ * vector form lets the last writer win -- is detected on the device and answered with GrB_INVALID_VALUE, naming the list.  An unsorted J
+ * that places 2^32 or more entries is GrB_NOT_IMPLEMENTED.  The scalar forms never materialise ni * nj values; without a mask, or under a
+ * complemented one, the dense region costs 4 ni nj bytes of column indices and is answered with GrB_OUT_OF_MEMORY before anything is
+ * allocated when they do not fit; an EMPTY GrB_Scalar is GrB_NOT_IMPLEMENTED.  GrB_Row_assign / GrB_Col_assign take a VECTOR mask over the
+ * row / column (replace touches that row / column only) and run through GrB_Vector_assign; i / j out of range: GrB_INVALID_INDEX.
+ * GrB_Matrix_setElement_<T> / _Scalar (the scalar form with one index each; an empty scalar removes the element) and
+ * GrB_Matrix_removeElement (the matrix form with an empty 1 x 1 input) each cost a pass over the matrix: O(nnz(C)) per call -- build a matrix
+ * with GrB_Matrix_build, not element by element.  Out-of-range indices: GrB_INVALID_INDEX. */
 GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
 GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
 GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc);

@@ -120,6 +120,9 @@ def _declare(L):
         getattr(L, f"GrB_Vector_assign_{t}").argtypes = [c_void_p, c_void_p, c_void_p, ct, c_void_p, c_u64, c_void_p]
         getattr(L, f"GrB_Vector_reduce_{t}").argtypes = [P(ct), c_void_p, c_void_p, c_void_p, c_void_p]
         getattr(L, f"GrB_Scalar_setElement_{t}").argtypes = [c_void_p, ct]
+        getattr(L, f"GrB_Matrix_setElement_{t}").argtypes = [c_void_p, ct, c_u64, c_u64]
+        # (C, Mask, accum, x, I, ni, J, nj, desc)
+        getattr(L, f"GrB_Matrix_assign_{t}").argtypes = [c_void_p, c_void_p, c_void_p, ct, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
         for kind in ("Matrix", "Vector"):  # (C, Mask, accum, op, A, y, desc)
             getattr(L, f"GrB_{kind}_select_{t}").argtypes = [c_void_p] * 5 + [ct, c_void_p]
             getattr(L, f"GrB_{kind}_apply_BinaryOp1st_{t}").argtypes = [c_void_p] * 4 + [ct, c_void_p, c_void_p]  # (C, Mask, accum, op, x, A, desc)
@@ -161,6 +164,13 @@ def _declare(L):
     L.GrB_Matrix_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
     L.GrB_Col_extract.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p]
     L.GrB_Matrix_extractElement_Scalar.argtypes = [c_void_p, c_void_p, c_u64, c_u64]
+    # (C, Mask, accum, A | s, I, ni, J, nj, desc) / (C, mask, accum, u, i, J, nj, desc) / (C, mask, accum, u, I, ni, j, desc)
+    L.GrB_Matrix_assign.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
+    L.GrB_Matrix_assign_Scalar.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
+    L.GrB_Row_assign.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p]
+    L.GrB_Col_assign.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p]
+    L.GrB_Matrix_setElement_Scalar.argtypes = [c_void_p, c_void_p, c_u64, c_u64]
+    L.GrB_Matrix_removeElement.argtypes = [c_void_p, c_u64, c_u64]
     L.GrX_option_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
     L.GrX_option_get.argtypes = [ctypes.c_char_p, P(ctypes.c_int64)]
     L.GrX_options_reset.argtypes = []

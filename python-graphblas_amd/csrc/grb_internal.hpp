@@ -207,6 +207,7 @@ void preload_prim();
 void preload_select();
 void preload_extract();
 void preload_apply();
+void preload_assign();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)
@@ -619,6 +620,16 @@ bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MD
 // C<Mask, replace> = accum(C, T) for T in C's type; T is released on every way out.  c_is_an_input: C is also an operand, whose
 // cached layouts go before the write rule
 void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input);
+
+// ---- the region merge of GrB_assign (grb_mxm_ewise.inc) ----
+struct MergeRegion {
+    const int32_t *rinv;              // per row of C: >= 0 = the row is assigned to; nullptr: every row
+    const unsigned long long *jbits;  // bit per column of C: the column is assigned to; nullptr: the range [jlo, jhi)
+    int64_t jlo, jhi;
+};
+// Z (fresh, C's type, one value per entry) = C merged with S (in C's type, sorted rows) over the union of the patterns, `op` where both
+// hold an entry.  reg != nullptr: an entry of C alone is dropped when it lies inside the region
+MatrixOwner matrix_merge_region(GB_Matrix_opaque *C, GB_Matrix_opaque *S, int op, const MergeRegion *reg);
 
 // ---- primitives implemented in grb_prim.hip (rocPRIM-backed) ---------------------------------------
 void prim_sort_pairs_u64_u32(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,

@@ -36,6 +36,11 @@ struct EwiseArgs {
     const int64_t *uoff;   // fill pass: where the unit writes
     int32_t *Tj;
     void *Tx;
+    // REGION kernels (GrB_assign without an accumulator, grb_assign.hip): an entry of A alone is dropped when its row is selected
+    // (rinv == nullptr: every row) and its column lies in the assigned columns (jbits == nullptr: the range [jlo, jhi))
+    const int32_t *rinv;
+    const unsigned long long *jbits;
+    int jlo, jhi;
 };
 
 template <typename T>
@@ -51,8 +56,9 @@ __device__ __forceinline__ bool ewise_compare(int op, T a, T b)
     }
 }
 
-// T: the operator's type (both operands are in it); CMP: `op` is a comparison and the result BOOL
-template <typename T, bool UNION, bool FILL, bool CMP>
+// T: the operator's type (both operands are in it); CMP: `op` is a comparison and the result BOOL; REGION: the assign flavour of the
+// union (EwiseArgs::rinv)
+template <typename T, bool UNION, bool FILL, bool CMP, bool REGION = false>
 __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
 {
     using TO = typename std::conditional<CMP, bool, T>::type;
@@ -79,6 +85,8 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
     int *sa = s_a[wv], *sb = s_b[wv];
     T *sbv = s_bv[wv];
     const int op = a.op;
+    bool row_in = false;  // (REGION, wave-uniform) the row is one of the assigned rows
+    if constexpr (REGION) row_in = a.rinv ? a.rinv[row] >= 0 : true;
     int64_t out = FILL ? a.uoff[unit] : 0, cnt = 0;
     // (the intersection is complete as soon as one list is: what the other still holds has no partner)
     while (UNION ? (pa < ea || pb < eb) : (pa < ea && pb < eb)) {
@@ -104,6 +112,9 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
             lb_b = chunk_lower_bound(sb, aj);
             const bool hb = lb_b < 64 && sb[lb_b] == aj;
             emit_a = UNION || hb;
+            if constexpr (REGION) {
+                if (!hb && row_in && (a.jbits ? ((a.jbits[aj >> 6] >> (aj & 63)) & 1ull) != 0 : (aj >= a.jlo && aj < a.jhi))) emit_a = false;
+            }
             if (FILL) {
                 if (hb) {
                     if constexpr (CMP) za = ewise_compare<T>(op, av, sbv[lb_b]);
@@ -142,10 +153,12 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
 }
 
 template <typename T>
-static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea)
+static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea, bool region = false)
 {
     const dim3 block(256);
-    if (is_add) {
+    if (region) {
+        hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, false, true>), grid, block, 0, ctx().stream, ea);
+    } else if (is_add) {
         if (cmp) hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, true>), grid, block, 0, ctx().stream, ea);
         else hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, false>), grid, block, 0, ctx().stream, ea);
     } else {
@@ -155,8 +168,9 @@ static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs 
 }
 
 // T (fresh storage, type `tt`) = A (op) B; Ax / Bx: the operands' values in the operator's type `ot` (one value when iso); both
-// operands hold entries
-static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op, bool is_add, bool cmp)
+// operands hold entries (or, an empty one, at least its row pointers).  reg: the assign flavour of the union
+static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op, bool is_add, bool cmp,
+                               const MergeRegion *reg = nullptr)
 {
     MatrixOwner Tm(matrix_new(type_of_code(tt), A->nrows, A->ncols));
     const int64_t m = (int64_t)A->nrows;
@@ -164,6 +178,7 @@ static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_op
     ea.Ap = A->d_ptr; ea.Aj = A->d_col; ea.Ax = Ax; ea.a_iso = A->iso ? 1 : 0;
     ea.Bp = B->d_ptr; ea.Bj = B->d_col; ea.Bx = Bx; ea.b_iso = B->iso ? 1 : 0;
     ea.op = op;
+    if (reg) { ea.rinv = reg->rinv; ea.jbits = reg->jbits; ea.jlo = (int)reg->jlo; ea.jhi = (int)reg->jhi; }
     const UnitTable ut = unit_table(ea.Ap, ea.Bp, m, (int64_t)A->ncols);
     if (ut.n_units == 0) {
         ctx().stats.kernel_launches += 2;
@@ -174,7 +189,8 @@ static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_op
     ea.ubase = ut.ubase.p; ea.urow = ut.urow.p; ea.n_units = ut.n_units; ea.piece_cols = ut.piece_cols; ea.ucount = uoff.p;
     const dim3 grid = ut.grid(), block(256);
     // (the count pass reads no value: one instantiation per pattern rule)
-    if (is_add) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false>), grid, block, 0, ctx().stream, ea);
+    if (reg) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false, true>), grid, block, 0, ctx().stream, ea);
+    else if (is_add) hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, true, false, false>), grid, block, 0, ctx().stream, ea);
     else hipLaunchKernelGGL((k_mat_ewise_wave<uint8_t, false, false, false>), grid, block, 0, ctx().stream, ea);
     prim_exclusive_sum_i64(uoff.p, uoff.p, ut.n_units + 1);
     d2h(&nnzT, uoff.p + ut.n_units, sizeof(int64_t));
@@ -185,7 +201,7 @@ static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_op
         Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzT);
         Tm->d_val = dev_alloc(type_size(tt) * (size_t)nnzT);
         ea.uoff = uoff.p; ea.Tj = Tm->d_col; ea.Tx = Tm->d_val;
-        GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea); })
+        GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea, reg != nullptr); })
         ctx().stats.kernel_launches += 2;
     }
     Tm->nvals = nnzT;
@@ -207,3 +223,16 @@ static MatrixOwner ewise_pass_through(GB_Matrix_opaque *S, int ot, int tt, int c
     return Tm;
 }
 
+// Z (fresh storage, C's type, one value per entry) = the union of C and S, `op` where both hold an entry; S is in C's type.  With `reg`
+// (GrB_assign without an accumulator: op = SECOND) an entry of C alone inside the region is dropped.  DESIGN.md section 4.10
+MatrixOwner matrix_merge_region(GB_Matrix_opaque *C, GB_Matrix_opaque *S, int op, const MergeRegion *reg)
+{
+    const int ct = C->type->code;
+    if (C->nvals == 0 || (S->nvals == 0 && !reg)) {
+        MatrixOwner Z(matrix_cast_copy(C->nvals ? C : S, ct));
+        matrix_expand_iso(Z.get());
+        return Z;
+    }
+    matrix_rowptr(S);
+    return ewise_merge(C, C->d_val, S, S->d_val, ct, ct, op, true, false, reg);
+}

@@ -11,8 +11,10 @@
 //   * the entry points of the operations this library does not accelerate, with their C API 2.0 signatures, returning
 //     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip;
 //     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip;
-//     GrB_{Matrix,Vector}_apply_{BinaryOp1st,BinaryOp2nd,IndexOp}_{<T>,Scalar}: grb_apply.hip.  The unary GrB_Matrix_apply /
-//     GrB_Vector_apply stay here: no kernel implements a unary operator.)
+//     GrB_{Matrix,Vector}_apply_{BinaryOp1st,BinaryOp2nd,IndexOp}_{<T>,Scalar}: grb_apply.hip; GrB_Matrix_assign, GrB_Matrix_assign_<T> /
+//     _Scalar, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_setElement_<T> / _Scalar, GrB_Matrix_removeElement: grb_assign.hip.  The unary
+//     GrB_Matrix_apply / GrB_Vector_apply stay here: no kernel implements a unary operator; so do kronecker, GrB_Matrix_diag and
+//     GrB_Matrix_reduce_BinaryOp.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -296,13 +298,7 @@ NI_M(GrB_Matrix_apply, const GrB_Matrix, const GrB_BinaryOp, const GrB_UnaryOp, 
 NI_MAT_BINARY(GrB_Matrix_kronecker_BinaryOp, GrB_BinaryOp)
 NI_MAT_BINARY(GrB_Matrix_kronecker_Monoid, GrB_Monoid)
 NI_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)
-NI_M(GrB_Matrix_assign, const GrB_Matrix, const GrB_BinaryOp, const GrB_Matrix, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
-NI_M(GrB_Row_assign, const GrB_Vector, const GrB_BinaryOp, const GrB_Vector, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
-NI_M(GrB_Col_assign, const GrB_Vector, const GrB_BinaryOp, const GrB_Vector, const GrB_Index *, GrB_Index, GrB_Index, const GrB_Descriptor)
 NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Descriptor)
-NI_M(GrB_Matrix_removeElement, GrB_Index, GrB_Index)
-NI_M(GrB_Matrix_assign_Scalar, const GrB_Matrix, const GrB_BinaryOp, const GrB_Scalar, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
-NI_M(GrB_Matrix_setElement_Scalar, const GrB_Scalar, GrB_Index, GrB_Index)
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Vector, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
@@ -329,8 +325,6 @@ extern "C" GrB_Info GrB_Semiring_new(GrB_Semiring *, GrB_Monoid, GrB_BinaryOp) {
         GRB_CATCH(errp(s))                                                                                                           \
     }                                                                                                                                \
     extern "C" GrB_Info GrB_Monoid_new_##NAME(GrB_Monoid *, GrB_BinaryOp, ctype) { return GrB_NOT_IMPLEMENTED; }                     \
-    NI_M(GrB_Matrix_setElement_##NAME, ctype, GrB_Index, GrB_Index)                                                                  \
-    extern "C" GrB_Info GrB_Matrix_reduce_##NAME(ctype *, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; } \
-    NI_M(GrB_Matrix_assign_##NAME, const GrB_Matrix, const GrB_BinaryOp, ctype, const GrB_Index *, GrB_Index, const GrB_Index *, GrB_Index, const GrB_Descriptor)
+    extern "C" GrB_Info GrB_Matrix_reduce_##NAME(ctype *, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 GRB_FOR_EACH_TYPE(DEF_SURFACE_TYPED)
 #undef DEF_SURFACE_TYPED

@@ -365,6 +365,56 @@ class Matrix(BaseType):
     def __matmul__(self, other):
         return InfixMatMul(self, other)
 
+    # ---- assign (reference core/matrix.py:3092-3300, core/expr.py:404-560 -> GrB_Matrix_assign & co.) -------------------------------
+    # ``Matrix.__setitem__`` / ``__delitem__`` are deliberately absent: ``C()[I, J] = A``, ``C()[I, J] << A`` and ``C[I, J] << A`` assign,
+    # ``C.remove_element(i, j)`` deletes.
+    @staticmethod
+    def _is_scalar_index(key):
+        def one(k):
+            return isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_))
+
+        return isinstance(key, tuple) and len(key) == 2 and one(key[0]) and one(key[1])
+
+    def _resolve_keys(self, keys):
+        if not isinstance(keys, tuple) or len(keys) != 2:
+            raise TypeError(f"Invalid index for a Matrix: a pair `C[rows, columns]` is required; got {keys!r}")
+        return _AxisIndex(keys[0], self._nrows), _AxisIndex(keys[1], self._ncols)
+
+    def _indexed_assigner(self, key, *, mask=None, accum=None, replace=False, opts=None):
+        """``C(mask, accum, replace)[I, J]``, ``[i, J]``, ``[I, j]`` on the left of ``<<`` / ``=``"""
+        rows, cols = self._resolve_keys(key)
+        return _MatrixAssigner(self, rows, cols, mask=mask, accum=accum, replace=replace, opts=opts)
+
+    def _element_assigner(self, key, accum=None):
+        """``C()[i, j]`` / ``C(accum)[i, j]`` on the left of ``<<`` / ``=``"""
+        rows, cols = self._resolve_keys(key)
+        return _MatrixAssigner(self, rows, cols, accum=accum)
+
+    def _assign_scalar_all(self, value, mask=None, accum=None, replace=False, *, opts):
+        """``C(mask, accum, replace) << scalar``: the scalar form of GrB_Matrix_assign over GrB_ALL x GrB_ALL (reference
+        core/base.py:352-372)."""
+        rows, cols = self._resolve_keys((slice(None), slice(None)))
+        _MatrixAssigner(self, rows, cols, mask=mask, accum=accum, replace=replace, opts=opts) << value
+
+    def _scalar_value(self, value):
+        from .base import Scalar
+
+        if isinstance(value, Scalar):
+            if value.is_empty:
+                raise ValueError("cannot assign an empty Scalar")
+            value = value.value
+        if not isinstance(value, (bool, int, float, np.generic)):
+            raise TypeError(f"Bad type for arg: {type(value).__name__}")
+        return self.dtype.np_type.type(value)
+
+    def remove_element(self, i, j):
+        """Delete the entry at (i, j), if there is one (``GrB_Matrix_removeElement``; the reference spells it ``del C[i, j]``).  Costs a
+        pass over the matrix: O(nvals)."""
+        rows, cols = self._resolve_keys((i, j))
+        if rows.scalar is None or cols.scalar is None:
+            raise TypeError("remove_element takes one row index and one column index")
+        call("GrB_Matrix_removeElement", [self, ctypes.c_uint64(rows.scalar), ctypes.c_uint64(cols.scalar)])
+
 
 class TransposedMatrix:
     """``A.T``: a view that only flips the descriptor's T0/T1 (reference core/matrix.py:3900-3960)."""
@@ -481,8 +531,8 @@ class _AxisIndex:
 class _MatrixElementExpr(ScalarExpression):
     """``A[i, j]``: read with ``.new()`` / ``.value`` / a comparison (reference core/matrix.py:3020-3050)."""
 
-    def __init__(self, matrix, row, col):
-        self.parent, self.row, self.col = matrix, row, col
+    def __init__(self, matrix, row, col, at=False):
+        self.parent, self.row, self.col, self._at = matrix, row, col, at
         super().__init__(self._read, matrix.dtype)
 
     def _read(self):
@@ -496,6 +546,25 @@ class _MatrixElementExpr(ScalarExpression):
         check_status(info, A)
         return A.dtype.np_type.type(out.value).item()
 
+    def _assigner(self, up=None):
+        one = lambda i, dim: _AxisIndex(i, dim)  # noqa: E731
+        A = self.parent
+        if self._at:
+            raise TypeError("'TransposedMatrix' object does not support item assignment")
+        rows, cols = one(self.row, A._nrows), one(self.col, A._ncols)
+        if up is None:
+            return _MatrixAssigner(A, rows, cols)
+        return _MatrixAssigner(A, rows, cols, mask=up.mask, accum=up.accum, replace=up.replace, opts=up.opts, sub=True)
+
+    def __call__(self, *args, **kwargs):
+        """``C[i, j](accum=op) << x`` (reference core/matrix.py:3092-3140)"""
+        return self._assigner(self.parent(*args, **kwargs))
+
+    def __lshift__(self, value):
+        self._assigner() << value
+
+    update = __lshift__
+
 
 def _extract(A, keys):
     if not isinstance(keys, tuple) or len(keys) != 2:
@@ -504,18 +573,153 @@ def _extract(A, keys):
     rows, cols = _AxisIndex(keys[0], A._nrows), _AxisIndex(keys[1], A._ncols)
     if rows.scalar is not None and cols.scalar is not None:
         i, j = (cols.scalar, rows.scalar) if at else (rows.scalar, cols.scalar)
-        return _MatrixElementExpr(base, i, j)
+        return _MatrixElementExpr(base, i, j, at)
     if rows.scalar is None and cols.scalar is None:
-        expr = Expression("extract", "GrB_Matrix_extract", [base, *rows.cargs, *cols.cargs], op=None, output_type=Matrix,
-                          shape=(rows.size, cols.size), at=at, dtype=base.dtype)
+        expr = _IndexedMatrix("extract", "GrB_Matrix_extract", [base, *rows.cargs, *cols.cargs], op=None, output_type=Matrix,
+                              shape=(rows.size, cols.size), at=at, dtype=base.dtype)
     else:
         # A[i, J] is the reference's spelling of GrB_Col_extract with T0 (row i of A); on A.T the roles swap
         row_form = rows.scalar is not None
         lst, j = (cols, rows.scalar) if row_form else (rows, cols.scalar)
-        expr = Expression("extract", "GrB_Col_extract", [base, *lst.cargs, ctypes.c_uint64(j)], op=None, output_type=Vector,
-                          shape=(lst.size,), at=row_form != at, dtype=base.dtype)
+        expr = _IndexedMatrix("extract", "GrB_Col_extract", [base, *lst.cargs, ctypes.c_uint64(j)], op=None, output_type=Vector,
+                              shape=(lst.size,), at=row_form != at, dtype=base.dtype)
     expr._index_arrays = (rows.array, cols.array)  # (the C call reads them: kept alive with the expression)
+    expr._target = (A, rows, cols)
     return expr
+
+
+class _IndexedMatrix(Expression):
+    """``A[I, J]`` / ``A[i, J]`` / ``A[I, j]``: on the right of ``<<`` (or with ``.new()``) it extracts; on the left it is an assign
+    target -- ``C[I, J] << A``, ``C[I, J]() << A``, ``C[i, J](accum=op) << v`` (the reference's AmbiguousAssignOrExtract, core/expr.py:
+    240-400; the matrix counterpart of ``IndexedVector``)."""
+
+    def _assigner(self, up=None):
+        A, rows, cols = self._target
+        if A._is_transposed:
+            raise TypeError("'TransposedMatrix' object does not support item assignment")
+        if up is None:
+            return _MatrixAssigner(A, rows, cols)
+        return _MatrixAssigner(A, rows, cols, mask=up.mask, accum=up.accum, replace=up.replace, opts=up.opts, sub=True)
+
+    def __call__(self, *args, **kwargs):
+        if self._target[0]._is_transposed:
+            raise TypeError("'TransposedMatrix' object does not support item assignment")
+        return self._assigner(self._target[0](*args, **kwargs))
+
+    def __lshift__(self, value):
+        self._assigner() << value
+
+    update = __lshift__
+
+
+class _MatrixAssigner:
+    """The left side of a Matrix assign with its output parameters resolved: ``<<`` / ``update`` run it.
+      both indices lists / slices   GrB_Matrix_assign (a Matrix or ``A.T``), GrB_Matrix_assign_<T> / _Scalar (a number or a Scalar)
+      one index an integer          GrB_Row_assign / GrB_Col_assign (a Vector; a number under a Vector mask), else the scalar form
+      both integers                 GrB_Matrix_setElement_<T>; an empty Scalar removes the element
+    ``sub``: the parameters came behind the index (``C[I, J](mask) << A``), the reference's SUBassign, whose mask has the shape of the
+    region: only the spellings where that is the same thing as assign are accepted."""
+
+    def __init__(self, parent, rows, cols, *, mask=None, accum=None, replace=False, opts=None, sub=False):
+        self.parent, self.rows, self.cols = parent, rows, cols
+        self.mask, self.accum, self.replace, self.opts, self.sub = mask, accum, replace, opts or {}, sub
+
+    def _desc(self, mask, **extra):
+        from .descriptor import lookup as descriptor_lookup
+
+        complement, structure = (mask.complement, mask.structure) if mask is not None else (False, False)
+        return descriptor_lookup(mask_complement=complement, mask_structure=structure, output_replace=self.replace, **extra, **self.opts)
+
+    def __lshift__(self, value):
+        from .base import Scalar, _is_python_scalar
+
+        C, rows, cols, mask, accum = self.parent, self.rows, self.cols, self.mask, self.accum
+        where = f"Matrix[{'i' if rows.scalar is not None else 'I'}, {'j' if cols.scalar is not None else 'J'}] = ..."
+        if isinstance(value, InfixMatMul):
+            value = value.new()
+        if isinstance(value, Expression):
+            value = value.new()
+        n_scalar = (rows.scalar is not None) + (cols.scalar is not None)
+        if isinstance(value, (list, np.ndarray)):
+            if n_scalar == 2:
+                raise TypeError(f"Bad type for arg `value` in {where}: {type(value).__name__}")
+            value = _dense_value(np.asarray(value), rows, cols, C)
+        is_scalar = isinstance(value, Scalar) or _is_python_scalar(value)
+        vmask = mask is not None and isinstance(mask.parent, Vector)
+        if accum is not None:
+            accum = get_typed_op(accum, C.dtype, kind="binary")
+            if accum.opclass == "Monoid":
+                accum = accum.binaryop
+        if n_scalar == 2:
+            if mask is not None:
+                raise TypeError("Unable to use Vector mask on single element assignment to a Matrix" if vmask else
+                                "Single element assign does not accept a submask")
+            if not is_scalar:
+                raise TypeError(f"Bad type for arg `value` in {where}: {type(value).__name__}")
+            return self._set_element(value, accum)
+        if n_scalar == 1:
+            row_form = rows.scalar is not None
+            lst, idx = (cols, rows.scalar) if row_form else (rows, cols.scalar)
+            if is_scalar and vmask:
+                # (a number into a row / column under a Vector mask: the vector form needs a vector -- a full one of the list's length)
+                value = Vector.from_coo(np.arange(lst.size, dtype=np.uint64), np.full(lst.size, C._scalar_value(value)), dtype=C.dtype,
+                                        size=lst.size)
+                is_scalar = False
+            if isinstance(value, Vector):
+                if mask is not None and not vmask:
+                    raise TypeError("Unable to use Matrix mask on a row or column assignment of a Vector; use a Vector mask")
+                i = ctypes.c_uint64(idx)
+                if row_form:
+                    return call("GrB_Row_assign", [C, mask, accum, value, i, *lst.cargs, self._desc(mask)])
+                return call("GrB_Col_assign", [C, mask, accum, value, *lst.cargs, i, self._desc(mask)])
+            if not is_scalar:
+                raise TypeError(f"Bad type for arg `value` in {where}: {type(value).__name__}")
+            one = _AxisIndex([idx], C._nrows if row_form else C._ncols)
+            rows, cols = (one, cols) if row_form else (rows, one)
+        if vmask:
+            raise TypeError("Unable to use Vector mask on Matrix assignment to a Matrix")
+        if self.sub and mask is not None and not (rows.array is None and cols.array is None and n_scalar == 0):
+            raise TypeError("C[I, J](mask) << value is a SUBassign (the mask has the shape of the region), which this library does not have; "
+                            "write C(mask)[I, J] << value with a mask of the shape of C")
+        if isinstance(value, (Matrix, TransposedMatrix)) and n_scalar == 0:
+            desc = self._desc(mask, transpose_first=value._is_transposed)
+            return call("GrB_Matrix_assign", [C, mask, accum, value._matrix, *rows.cargs, *cols.cargs, desc])
+        if not is_scalar:
+            raise TypeError(f"Bad type for arg `value` in {where}: {type(value).__name__}")
+        if isinstance(value, Scalar):
+            from .base import GrBScalarArg
+
+            return call("GrB_Matrix_assign_Scalar", [C, mask, accum, GrBScalarArg(value), *rows.cargs, *cols.cargs, self._desc(mask)])
+        ctype = np.ctypeslib.as_ctypes_type(C.dtype.np_type)
+        return call(f"GrB_Matrix_assign_{C.dtype.name}", [C, mask, accum, ctype(C._scalar_value(value).item()), *rows.cargs, *cols.cargs,
+                                                          self._desc(mask)])
+
+    update = __lshift__
+
+    def _set_element(self, value, accum):
+        from .base import Scalar, _apply_host_binary
+
+        C, i, j = self.parent, self.rows.scalar, self.cols.scalar
+        if isinstance(value, Scalar) and value.is_empty:
+            return C.remove_element(i, j)
+        x = C._scalar_value(value)
+        if accum is not None:
+            old = _MatrixElementExpr(C, i, j).value
+            if old is not None:
+                x = C.dtype.np_type.type(_apply_host_binary(accum.name, C.dtype.np_type.type(old), x))
+        ctype = np.ctypeslib.as_ctypes_type(C.dtype.np_type)
+        call(f"GrB_Matrix_setElement_{C.dtype.name}", [C, ctype(x.item()), ctypes.c_uint64(i), ctypes.c_uint64(j)])
+
+
+def _dense_value(a, rows, cols, C):
+    """A list / array on the right of an assign: a full Matrix or Vector of the region's shape (reference tests/test_matrix.py:1759-1781)."""
+    want = tuple(ax.size for ax in (rows, cols) if ax.scalar is None)
+    if a.shape != want:
+        raise ValueError(f"shape mismatch: value array of shape {a.shape} does not match indexing of shape {want}")
+    if a.ndim == 1:
+        return Vector.from_coo(np.arange(a.size, dtype=np.uint64), a, size=a.size)
+    r, c = np.divmod(np.arange(a.size, dtype=np.uint64), np.uint64(max(a.shape[1], 1)))
+    return Matrix.from_coo(r, c, a.ravel(), nrows=a.shape[0], ncols=a.shape[1])
 
 
 def _reduce_vector(A, op, method_name, transpose):
