@@ -299,7 +299,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C) */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C) */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */
@@ -492,6 +492,10 @@ GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseAdd_Semiring, GrB_Semiring)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_BinaryOp, GrB_BinaryOp)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_Monoid, GrB_Monoid)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_Semiring, GrB_Semiring)
+/* GrB_kronecker (C API 2.0 section 4.3.11; grb_kron.hip): C<Mask, replace> = accum(C, T), T of shape
+ * (ma mb) x (na nb) with T[ia mb + ib, ja nb + jb] = op(A[ia, ja], B[ib, jb]); T0 / T1 transpose A / B; the _Semiring form takes the
+ * multiply operator.  na nb > 2^31 - 1 is GrB_NOT_IMPLEMENTED (int32 column indices), a product whose entries or row pointers do not
+ * fit GrB_OUT_OF_MEMORY; C is unchanged on every failure. */
 GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_BinaryOp, GrB_BinaryOp)
 GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_Monoid, GrB_Monoid)
 GRB_DECL_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)

@@ -111,6 +111,8 @@ def _declare(L):
         for call in ("eWiseAdd", "eWiseMult"):
             for opclass in ("BinaryOp", "Monoid", "Semiring"):
                 getattr(L, f"GrB_{kind}_{call}_{opclass}").argtypes = [c_void_p] * 7
+    for opclass in ("BinaryOp", "Monoid", "Semiring"):
+        getattr(L, f"GrB_Matrix_kronecker_{opclass}").argtypes = [c_void_p] * 7
     for t, ct in (("BOOL", ctypes.c_bool), ("INT8", ctypes.c_int8), ("INT16", ctypes.c_int16), ("INT32", ctypes.c_int32),
                   ("INT64", ctypes.c_int64), ("UINT8", ctypes.c_uint8), ("UINT16", ctypes.c_uint16), ("UINT32", ctypes.c_uint32),
                   ("UINT64", ctypes.c_uint64), ("FP32", ctypes.c_float), ("FP64", ctypes.c_double)):

@@ -12,9 +12,9 @@
 //     GrB_NOT_IMPLEMENTED and leaving a message for GrB_*_error.  (GrB_Matrix_select_* / GrB_Vector_select_* are real: grb_select.hip;
 //     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip;
 //     GrB_{Matrix,Vector}_apply_{BinaryOp1st,BinaryOp2nd,IndexOp}_{<T>,Scalar}: grb_apply.hip; GrB_Matrix_assign, GrB_Matrix_assign_<T> /
-//     _Scalar, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_setElement_<T> / _Scalar, GrB_Matrix_removeElement: grb_assign.hip.  The unary
-//     GrB_Matrix_apply / GrB_Vector_apply stay here: no kernel implements a unary operator; so do kronecker, GrB_Matrix_diag and
-//     GrB_Matrix_reduce_BinaryOp.)
+//     _Scalar, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_setElement_<T> / _Scalar, GrB_Matrix_removeElement: grb_assign.hip;
+//     GrB_Matrix_kronecker_* in all three operator forms: grb_kron.hip.  The unary GrB_Matrix_apply / GrB_Vector_apply stay here: no
+//     kernel implements a unary operator; so do GrB_Matrix_diag and GrB_Matrix_reduce_BinaryOp.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -294,10 +294,6 @@ static GrB_Info not_impl(GB_Vector_opaque *w, const char *fn)
 
 NI_V(GrB_Vector_apply, const GrB_Vector, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Vector, const GrB_Descriptor)
 NI_M(GrB_Matrix_apply, const GrB_Matrix, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Matrix, const GrB_Descriptor)
-#define NI_MAT_BINARY(FN, HANDLE) NI_M(FN, const GrB_Matrix, const GrB_BinaryOp, const HANDLE, const GrB_Matrix, const GrB_Matrix, const GrB_Descriptor)
-NI_MAT_BINARY(GrB_Matrix_kronecker_BinaryOp, GrB_BinaryOp)
-NI_MAT_BINARY(GrB_Matrix_kronecker_Monoid, GrB_Monoid)
-NI_MAT_BINARY(GrB_Matrix_kronecker_Semiring, GrB_Semiring)
 NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Descriptor)
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }

@@ -329,6 +329,11 @@ class Matrix(BaseType):
         ``GrB_Matrix_eWiseMult_<opclass>``)."""
         return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
 
+    def kronecker(self, other, op=_binary.times):
+        """``C << A.kronecker(B, op)``: the Kronecker product, ``C[ia*mb + ib, ja*nb + jb] = op(A[ia, ja], B[ib, jb])`` (reference
+        core/matrix.py:2333-2373 -> C ``GrB_Matrix_kronecker_<opclass>``)."""
+        return _kronecker(self, other, op)
+
     def reduce_rowwise(self, op="plus"):
         return _reduce_vector(self, op, "reduce_rowwise", False)
 
@@ -451,6 +456,10 @@ class TransposedMatrix:
         """``C << A.ewise_mult(B, op)``: intersection of the patterns (reference core/matrix.py ewise_mult -> C
         ``GrB_Matrix_eWiseMult_<opclass>``)."""
         return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
+
+    def kronecker(self, other, op=_binary.times):
+        """``C << A.T.kronecker(B, op)``: the product runs on the transpose (descriptor T0)."""
+        return _kronecker(self, other, op)
 
     def reduce_rowwise(self, op="plus"):
         return _reduce_vector(self, op, "reduce_rowwise", False)
@@ -881,6 +890,14 @@ def _ewise(A, B, op, method_name, cfunc):
     if A.shape != B.shape:
         expr._force_library_error()
     return expr
+
+
+def _kronecker(A, B, op):
+    if not isinstance(B, (Matrix, TransposedMatrix)):
+        raise TypeError(f"Expected type: Matrix; got {type(B).__name__}")
+    op = get_typed_op(op, A.dtype, B.dtype, kind="binary")  # (a BinaryOp or a Monoid; a Semiring is a TypeError, as in the reference)
+    return Expression("kronecker", f"GrB_Matrix_kronecker_{op.opclass}", [A._matrix, B._matrix], op=op, output_type=Matrix,
+                      shape=(A._nrows * B._nrows, A._ncols * B._ncols), at=A._is_transposed, bt=B._is_transposed)
 
 
 def _mxm(A, B, op):
