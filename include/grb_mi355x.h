@@ -312,6 +312,7 @@ typedef struct {
     int64_t long_probe;       /* BOOL product under a terminal monoid (LOR.LAND, ANY.PAIR): entries of every admitted long row tested bottom-up before the item kernels (0 = not probed) */
     int64_t long_tails;       /* 1: the cold entries of the long rows below the hub level ran with the short rows (sorted row tiles / tagged row groups), merged with the strips' accumulators (option "cold_in_rows") */
     int64_t pinned_natural;   /* 1: the product would have taken the matrix's popularity-ordered layouts but one of its vectors is pinned to the natural order (an exported device view, GrX_Vector_pin_natural): it ran the natural-order layouts */
+    int64_t cold_tile_mode;   /* mxv/vxm: layout of the cold tiles k_mxv_ctile ran on (0 three streams, 1 / 2 slot and column offset in one word -- option "ctile_pack" --, 3 value code and column in one word -- option "ctile_code"); -1: the call ran no cold tiles */
 } GrX_Stats;
 GrB_Info GrX_last_stats(GrX_Stats *stats);
 /* T = A (+.x) B in row batches of A whose products fit `budget_bytes` of device memory; every batch runs the full two-pass
@@ -366,6 +367,11 @@ GrB_Info GrX_Matrix_cache_bytes(const GrB_Matrix A, uint64_t *bytes);
  *                   natural-order layouts of hot-coded matrices too (measured slower there)
  *   "lazy_tagged"   (round 6) 1 (default): a matrix whose short rows have sorted row tiles lays the entries of its tagged row groups out only when a call
  *                   arrives that the tiles do not take (another semiring, a sparse operand that cannot be filled) -- from the tiles; 0: at layout build
+ *   "ctile_code"    (round 7) 1 (default): the cold tiles of a matrix with a value dictionary (a 4-byte type other than BOOL, not iso) whose operand
+ *                   image has at most 2^24 column codes keep an entry's value code and column code in one 32-bit word (code << 24 | column) next to its
+ *                   16-bit row slot -- 6 instead of 10 bytes per entry, no value stream (GrX_Stats.cold_tile_mode 3); any other matrix keeps three
+ *                   streams; 0: three streams for every matrix.  Applies with "ctile_pack" = 0.  Setting "ctile_pack" to ANY value, 0 included, names the
+ *                   layout of the cold tiles and stores 0 here; set "ctile_code" after it to have the code words again.  GrX_options_reset restores both.
  *   "ctile_pack"    (round 6) 0 (default; 0 .. 2; measured: no gain): 1: the cold tiles of an ordered matrix keep an entry's column (as an offset in its
  *                   column range, every range below 2^19 codes) and its row slot in one 32-bit word -- tiles of 8192 rows, 8 instead of 10 bytes per
  *                   entry; 2: and one-byte dictionary codes for the values (5 bytes per entry); 0: three streams

@@ -250,6 +250,9 @@ bool known_debug_flags(int64_t &v) { return !((int)v & ~DEBUG_FLAGS_MASK); }
 bool short_kernel_exists(int64_t &v) { return v != 2 && v != 3 && v != 4; }
 bool snap_long_classes(int64_t &v) { if (v != 16 && v != 32 && v != 64) v = 8; return true; }
 bool window_group(int64_t &v) { return (v & (v - 1)) == 0; }  // (0, 1, 2, 4, 8)
+// (whoever sets "ctile_pack" names the layout of the cold tiles -- 0, the three streams, included: the code words, which are on by default, give way
+//  until "ctile_code" is set again.  GrX_options_reset stores both, in the table's order, and so returns to what GrB_init left.)
+bool explicit_cold_layout(int64_t &) { ctx().ctile_code = 0; return true; }
 bool release_cache_when_off(int64_t &v) { if (!v) dev_cache_release(); return true; }
 
 const Option OPTIONS[] = {
@@ -290,7 +293,8 @@ const Option OPTIONS[] = {
     opt("fill_absent", &Context::fill_absent, Option::WITHIN, 0, 1),
     opt("rows_tile", &Context::rows_tile, Option::WITHIN, 0, 2),
     opt("lazy_tagged", &Context::lazy_tagged, Option::WITHIN, 0, 1),
-    opt("ctile_pack", &Context::ctile_pack, Option::WITHIN, 0, 2),
+    opt("ctile_pack", &Context::ctile_pack, Option::WITHIN, 0, 2, explicit_cold_layout),
+    opt("ctile_code", &Context::ctile_code, Option::WITHIN, 0, 1),  // (behind ctile_pack: GrB_init and GrX_options_reset store the rows in this order)
     opt("strip_slot16", &Context::strip_slot16, Option::WITHIN, 0, 1),
     opt("rtile_pack", &Context::rtile_pack, Option::WITHIN, 0, 1),
     opt("cold_in_rows", &Context::cold_in_rows, Option::CLAMP, 0, P30),

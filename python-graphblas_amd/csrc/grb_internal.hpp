@@ -150,6 +150,11 @@ struct Context {
     int lazy_tagged = 1;             // (round 6) 1: a matrix whose short rows have sorted row tiles builds the tagged row groups' ENTRIES (the layout of the calls the
                                      // tiles do not take) only when such a call arrives -- from the tiles; their offsets and "row has an entry" words are always built.
                                      // Scale 24: 0.32 GB less cached layouts and 2.3 ms less layout build when every call takes the tiles
+    int ctile_code = 1;              // (round 7) 1: with ctile_pack = 0 the cold tiles of a dictionary-coded 4-byte matrix whose image has at most 2^24 codes keep
+                                     // code << 24 | column code in the column word, the 16-bit slots and the tiles of the three-stream layout, no value stream: 6 instead
+                                     // of 10 bytes per entry, two loads per unit (cold-tile mode 3).  Headline k_mxv_ctile 139.4 -> 119.1 us, call 0.473 -> 0.451 ms
+                                     // (profiles/r07/ctile_code_word.txt).  Any other matrix: three streams.  Setting ctile_pack -- to 0 too -- stores 0 here
+                                     // (grb_context.hip: whoever names a layout gets that layout); set ctile_code behind it to have both
     int ctile_pack = 0;              // (round 6, MEASURED AND OFF) cold tiles of an ordered matrix with every column range below 2^19 codes: 1 = an entry's column (offset in
                                      // its range) and row slot in ONE word (slot << 19 | column; tiles of 8192 slots, up to 128 ranges): 8 instead of 10 bytes per
                                      // entry; 2 = ... and one-byte dictionary codes for its value (5 bytes).  Headline 0.461-0.471 ms with three streams, 0.471-0.479
@@ -407,7 +412,8 @@ struct GB_Matrix_opaque {
         int64_t ct_ntiles = 0;
         int64_t ct_units = 0;
         int ct_mode = 0;                   // (Context::ctile_pack) 0: d_ct_col / d_ct_val / d_ct_loc as three streams; 1: d_ct_col holds slot << 19 | (column - base of
-                                           // the tile's column range), no d_ct_loc, the tiles' range bases behind the CTile array; 2: ... and d_ct_val holds one-byte codes
+                                           // the tile's column range), no d_ct_loc, the tiles' range bases behind the CTile array; 2: ... and d_ct_val holds one-byte codes;
+                                           // 3: d_ct_col holds code << 24 | column code, d_ct_loc as in mode 0 (the padding's slot is one past the tile's), no d_ct_val
         uint64_t bytes(uint64_t vs) const; // (grb_mxv.hip)
     };
     // the short rows as tagged row groups (k_mxv_rows_tag; short_kernel = 5): per group of 64 rows its entries contiguous, padded to a

@@ -385,6 +385,11 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
             // range) and row slot of an entry in one word -- slot << 19 | column: tiles of 8192 slots --, mode 2 also one-byte value codes
             int ct_mode = 0;
             std::vector<int32_t> h_bounds;
+            // Round 7 (ctile_code = 1, the default, with ctile_pack = 0: mode 3): a dictionary-coded 4-byte matrix whose image has at most 2^24 codes (ncols, + hot_k in natural order: the
+            // bound of rtile_pack) keeps code << 24 | column code in the column word and drops the value stream -- 6 instead of 10 bytes per entry;
+            // slots, tiles, pieces and column ranges are those of mode 0.  Any other matrix takes mode 0.
+            if (kind == 4 && ctx().ctile_code == 1 && ctx().ctile_pack == 0 && A->vd.vdict_n > 0 && A->type->size == 4 && A->type->code != TC_BOOL && !A->iso && codes_total <= ((int64_t)1 << 24))
+                ct_mode = 3;
             if (kind == 4 && own_ranges && ctx().ctile_pack > 0) {
                 h_bounds.resize((size_t)A->order.ct_ncr + 1);
                 d2h(h_bounds.data(), A->order.d_cold_bounds, sizeof(int32_t) * h_bounds.size());
@@ -392,7 +397,8 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 for (int r = 0; r < A->order.ct_ncr; r++) widest = std::max<int64_t>(widest, (int64_t)h_bounds[(size_t)r + 1] - (int64_t)h_bounds[(size_t)r]);
                 if (widest < ((int64_t)1 << 19) - 1) ct_mode = (ctx().ctile_pack == 2 && A->vd.vdict_n > 0 && A->type->size == 4 && !A->iso) ? 2 : 1;
             }
-            const int ct_slots = ct_mode ? CT_PACK_SLOTS : (A->type->size > 4 ? CT_SLOTS / 2 : CT_SLOTS);  // (CtSlots<W>: 8-byte accumulators take half the slots)
+            const bool ct_packed = ct_mode == 1 || ct_mode == 2;  // (slot and column offset in one word)
+            const int ct_slots = ct_packed ? CT_PACK_SLOTS : (A->type->size > 4 ? CT_SLOTS / 2 : CT_SLOTS);  // (CtSlots<W>: 8-byte accumulators take half the slots)
             const int n_sb = (int)ceil_div(nl, (int64_t)ct_slots);
             const int64_t n_tiles = kind == 4 ? (int64_t)n_cr * n_sb : 0;
             std::vector<int64_t> h_first((size_t)n_tiles + 1, 0);
@@ -569,9 +575,12 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 }
             }
             // (measured, profiles/r04/value_dict.txt: one-byte codes make the tagged row groups 5 % faster -- 9 -> 6 bytes per entry of a
-            //  kernel that streams them all -- and the cold tiles 7 % SLOWER: their stream is a third of their time, the code load + LDS
-            //  lookup per entry costs more than the bytes it saves.  The tiles keep full values.)
-            const bool use_dict_all = ct_mode == 2;  // (round 6: behind the packed words the codes were measured again -- profiles/r06/ctile_pack.txt)
+            //  kernel that streams them all -- and the cold tiles 7 % SLOWER.  That round-4 figure was for the codes as a byte stream of their
+            //  own: a third load per unit next to the column and slot streams, 7 instead of 10 bytes per entry.  Round 6 measured the codes
+            //  again behind the packed words of mode 1 -- mode 2, still a load of their own: neutral, profiles/r06/ctile_pack.txt.  Round 7,
+            //  mode 3: the code rides in the top byte of the column word -- no load of its own, no value stream; profiles/r07/ctile_code_word.txt.
+            //  In mode 0 the tiles keep full values.)
+            const bool use_dict_all = ct_mode == 2 || ct_mode == 3;
             if (kind == 4 && nnz_long > n_strip) {
                 // the cold entries as tagged tiles: a (column range, slot block) pair is one tile, or several when it holds more than
                 // CT_MAX_ENTRIES entries (the hub rows: the sorted run is cut into equal pieces -- a piece still lies inside the
@@ -631,7 +640,7 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 // (packed: behind the nt tile records, the first column code of every tile's range -- int32[nt])
                 sp.cold.d_ct_tiles.reset(dev_alloc((sizeof(CTile) + sizeof(int32_t)) * (size_t)std::max<int64_t>(nt, 1)));
                 h2d(sp.cold.d_ct_tiles, h_tiles.data(), sizeof(CTile) * (size_t)nt);
-                if (ct_mode) {
+                if (ct_packed) {
                     std::vector<int32_t> h_cbase((size_t)nt);
                     for (int64_t t = 0; t < nt; t++) h_cbase[(size_t)t] = h_bounds[(size_t)tile_range[(size_t)t]];
                     h2d((char *)sp.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1), h_cbase.data(), sizeof(int32_t) * (size_t)nt);
@@ -642,11 +651,15 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                 h2d(efirst.p, h_efirst.data(), sizeof(int64_t) * (size_t)(nt + 1));
                 sp.cold.d_ct_col.reset((int32_t *)dev_alloc(sizeof(int32_t) * ents));
                 const size_t ct_vb = use_dict_all ? 1 : A->type->size;  // (dictionary-coded matrices: one byte per value)
-                sp.cold.d_ct_val.reset(A->iso ? nullptr : dev_alloc(ct_vb * ents));
-                sp.cold.d_ct_loc.reset(ct_mode ? nullptr : (uint16_t *)dev_alloc(sizeof(uint16_t) * ents));
+                sp.cold.d_ct_val.reset((A->iso || ct_mode == 3) ? nullptr : dev_alloc(ct_vb * ents));  // (mode 3: the codes ride in the column words)
+                sp.cold.d_ct_loc.reset(ct_packed ? nullptr : (uint16_t *)dev_alloc(sizeof(uint16_t) * ents));
                 GRB_HIP(hipMemsetAsync(sp.cold.d_ct_col, 0xff, sizeof(int32_t) * ents, ctx().stream));  // (padding: column -1 / the packed word 0xffffffff)
                 if (sp.cold.d_ct_val) GRB_HIP(hipMemsetAsync(sp.cold.d_ct_val, 0, ct_vb * ents, ctx().stream));
                 if (sp.cold.d_ct_loc) GRB_HIP(hipMemsetAsync(sp.cold.d_ct_loc, 0, sizeof(uint16_t) * ents, ctx().stream));
+                // (mode 3: the padding word 0xffffffff is also the entry (column 2^24 - 1, code 255) -- padding is told by its slot, ct_slots)
+                if (ct_mode == 3 && nt > 0)
+                    hipLaunchKernelGGL(k_ctile_pad_slots, dim3((unsigned)ceil_div(nt, 256)), dim3(256), 0, ctx().stream, (const CTile *)sp.cold.d_ct_tiles.get(),
+                                       (const int64_t *)efirst.p, nt, sp.cold.d_ct_loc.get(), (uint16_t)ct_slots);
                 const int64_t n_cold = nnz_long - n_strip;
                 {
                     // inside a tile the entries go by column code: neighbouring lanes gather from the same lines (grb_mxv_ctile.inc)
@@ -663,7 +676,8 @@ static void ensure_split(GB_Matrix_opaque *A, const int32_t *col_src, bool hot)
                                            (const CTile *)sp.cold.d_ct_tiles.get(), (const T *)A->d_val, A->iso ? 1 : 0, sp.cold.d_ct_col, (T *)sp.cold.d_ct_val.get(), sp.cold.d_ct_loc,
                                            use_dict_all ? (const unsigned long long *)A->vd.d_vd_table : (const unsigned long long *)nullptr,
                                            use_dict_all ? (const unsigned char *)A->vd.d_vd_codes : (const unsigned char *)nullptr,
-                                           ct_mode ? (const int32_t *)((const char *)sp.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1)) : (const int32_t *)nullptr);
+                                           ct_packed ? (const int32_t *)((const char *)sp.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(nt, 1)) : (const int32_t *)nullptr,
+                                           ct_mode == 3 ? 1 : 0);
                     })
                     sync_stream();
                 }
@@ -779,7 +793,7 @@ static uint64_t order_signature()
     const Context &c = ctx();
     uint64_t h = 1469598103934665603ull;
     const int64_t v[] = {c.long_kernel, c.short_kernel, c.long_classes, c.split_min_len, c.long_sub, c.long_sub_min_len, c.lean_min_nnz,
-                         c.split_min_nnz, c.hot_k, c.drop_hot_cols, c.hub_min_len, c.value_dict, c.rows_tile, c.rtile_rows, c.rtile_entries, c.cold_in_rows, c.rtile_pack, c.strip_slot16, c.ctile_pack, c.lazy_tagged};
+                         c.split_min_nnz, c.hot_k, c.drop_hot_cols, c.hub_min_len, c.value_dict, c.rows_tile, c.rtile_rows, c.rtile_entries, c.cold_in_rows, c.rtile_pack, c.strip_slot16, c.ctile_pack, c.ctile_code, c.lazy_tagged};
     for (int64_t x : v) h = (h ^ (uint64_t)x) * 1099511628211ull;
     return h;
 }
@@ -1274,11 +1288,19 @@ static void launch_pull_ipt(GB_Matrix_opaque *A, PullArgs &a)
                     a.ct_loc = A->split.cold.d_ct_loc;
                     a.ct_tiles = (const CTile *)A->split.cold.d_ct_tiles.get();
                     a.ct_mode = A->split.cold.ct_mode;
-                    a.ct_cbase = A->split.cold.ct_mode ? (const int32_t *)((const char *)A->split.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(A->split.cold.ct_ntiles, 1)) : nullptr;
-                    if (A->split.cold.ct_mode == 2) a.vdict = A->vd.d_vdict;  // (the cold tiles' values are dictionary codes)
+                    const int ctm = A->split.cold.ct_mode;
+                    a.ct_cbase = (ctm == 1 || ctm == 2) ? (const int32_t *)((const char *)A->split.cold.d_ct_tiles.get() + sizeof(CTile) * (size_t)std::max<int64_t>(A->split.cold.ct_ntiles, 1)) : nullptr;
+                    if (ctm == 2 || ctm == 3) a.vdict = A->vd.d_vdict;  // (the cold tiles' values are dictionary codes)
+                    ctx().stats.cold_tile_mode = ctm;
                     a.ct_order = A->split.cold.d_ct_order;
                     for (int x = 0; x <= 8; x++) a.ct_xoff[x] = A->split.cold.ct_xoff[x];
                     const int64_t Gt = std::max<int64_t>(8, (int64_t)(ctx().num_cus * CT_WGS_PER_CU / 8) * 8);
+                    if (ctm == 3) {  // (code << 24 | column words: a kernel of its own; the builder takes the mode for 4-byte types other than BOOL only)
+                        if constexpr (sizeof(T) == 4 && !std::is_same<T, bool>::value)
+                            hipLaunchKernelGGL((k_mxv_ctile<T, MON, MUL, true>), dim3((unsigned)Gt), dim3(CT_BLOCK), 0, ctx().stream, a);
+                        else
+                            fail(GrB_PANIC, "cold tiles: code words built for a type that has no kernel for them (internal error)");
+                    } else
                     hipLaunchKernelGGL((k_mxv_ctile<T, MON, MUL>), dim3((unsigned)Gt), dim3(CT_BLOCK), 0, ctx().stream, a);
                     ctx().stats.kernel_launches += 1;
                 };
@@ -1615,6 +1637,7 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     ctx().stats = GrX_Stats{};
     ctx().stats.method = 1;
     ctx().stats.long_kernel = -1;
+    ctx().stats.cold_tile_mode = -1;
     ctx().stats.flops = S->nvals;
     ctx().stats.out_nvals = -1;
     const int64_t m = (int64_t)w->n;
@@ -2066,6 +2089,7 @@ static int push_thin(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     ctx().stats.method = 2;
     ctx().stats.out_nvals = -1;
     ctx().stats.long_kernel = -1;
+    ctx().stats.cold_tile_mode = -1;
     PushThin a{};
     a.u_bits = u->d_bits;
     a.n_in = n_in;

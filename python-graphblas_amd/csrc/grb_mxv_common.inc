@@ -74,8 +74,9 @@ struct PullArgs {
     const void *ct_val;
     const uint16_t *ct_loc;
     const struct CTile *ct_tiles;
-    int ct_mode;                      // 0 three streams; 1 packed words (slot << 19 | column - ct_cbase[tile]), tiles of 8192 slots; 2 ... + one-byte value codes
-    const int32_t *ct_cbase;          // (ct_mode > 0) per tile: the first column code of its range
+    int ct_mode;                      // 0 three streams; 1 packed words (slot << 19 | column - ct_cbase[tile]), tiles of 8192 slots; 2 ... + one-byte value codes;
+                                      // 3 (k_mxv_ctile<.., CODEW>) ct_col holds code << 24 | column code, ct_loc the slots as in mode 0, no ct_val
+    const int32_t *ct_cbase;          // (ct_mode 1 and 2) per tile: the first column code of its range
     const int32_t *ct_order;          // tile numbers in walking order: XCD x takes ct_order[ct_xoff[x] .. ct_xoff[x + 1]), column range after column range
     int64_t ct_xoff[9];
     const char *hrec;                 // hot strips (k_mxv_strip<..., HOT = 1>): lane records [8 LDS slots | 8 values], see GB_Matrix_opaque::d_hrec

@@ -84,7 +84,7 @@ __global__ void k_ctile_keys2(const uint32_t *sidx, int64_t p0, int64_t n_cold, 
 template <typename T>
 __global__ void k_ctile_place(const uint64_t *skeys, const uint32_t *sidx, int64_t p0, int64_t n_cold, const uint64_t *key2s, const uint32_t *pays,
                               const int64_t *efirst, const CTile *tiles, const T *val, int iso, int32_t *tcol, T *tval, uint16_t *tloc,
-                              const unsigned long long *vd_table, const unsigned char *vd_codes, const int32_t *cbase)
+                              const unsigned long long *vd_table, const unsigned char *vd_codes, const int32_t *cbase, int code_word)
 {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (place in the (tile, code) order)
     if (q >= n_cold) return;
@@ -100,8 +100,10 @@ __global__ void k_ctile_place(const uint64_t *skeys, const uint32_t *sidx, int64
     else tcol[d] = (int32_t)(uint32_t)k2;
     bool coded = false;
     if constexpr (sizeof(T) == 4) {
-        if (vd_table) {  // dictionary-coded values (grb_mxv_vdict.inc): tval is a byte array
-            ((unsigned char *)tval)[d] = (unsigned char)vdict_code(vd_table, vd_codes, ((const uint32_t *)val)[sidx[p]]);
+        if (vd_table) {  // dictionary-coded values (grb_mxv_vdict.inc): tval is a byte array -- or (code_word, ct_mode 3) the code rides in the column word
+            const uint32_t code = (uint32_t)vdict_code(vd_table, vd_codes, ((const uint32_t *)val)[sidx[p]]) & 0xffu;
+            if (code_word) tcol[d] = (int32_t)((code << 24) | ((uint32_t)k2 & 0x00ffffffu));  // (the host takes this mode below 2^24 column codes only)
+            else ((unsigned char *)tval)[d] = (unsigned char)code;
             coded = true;
         }
     }
@@ -109,13 +111,28 @@ __global__ void k_ctile_place(const uint64_t *skeys, const uint32_t *sidx, int64
     if (tloc) tloc[d] = (uint16_t)(slot - tiles[t].base);
 }
 
-template <typename T, int MONOID_CT, int MULT_CT>
+// ct_mode 3: a padding entry cannot be told by its WORD -- 0xffffffff is the real entry (column 2^24 - 1, code 255) -- so it is told by its SLOT:
+// the padding behind a tile's last entry carries slot CT_SLOTS, one past the tile's rows, whose bit in the spare word of s_off is always set.
+// The kernel then treats it like an entry of a masked-out row: column -1, an out-of-range address, nothing gathered, no product (as mode 0
+// does with its padding column -1).
+__global__ void k_ctile_pad_slots(const CTile *tiles, const int64_t *efirst, int64_t n_tiles, uint16_t *tloc, uint16_t pad_slot)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tiles) return;
+    const int64_t d0 = tiles[t].u0 * CT_EPL, d1 = d0 + (int64_t)tiles[t].n_units * CT_EPL;
+    for (int64_t d = d0 + (efirst[t + 1] - efirst[t]); d < d1; d++) tloc[d] = pad_slot;  // (at most CT_EPL - 1 of them)
+}
+
+// CODEW (PullArgs::ct_mode 3, 4-byte types with a value dictionary): an entry is the word code << 24 | column code and a 16-bit slot -- two
+// stream loads per unit, the value from the dictionary in LDS (as k_mxv_rtile<.., DICT, PACK>)
+template <typename T, int MONOID_CT, int MULT_CT, bool CODEW = false>
 __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
 {
     using W = typename Widen<T>::type;
     constexpr int EPL = CT_EPL, SLOTS = CtSlots<W>::value;
+    static_assert(!CODEW || (sizeof(T) == 4 && !std::is_same<T, bool>::value && SLOTS == CT_SLOTS), "code words: 4-byte values, tiles of CT_SLOTS slots");
     __shared__ W s_acc[SLOTS];
-    __shared__ uint32_t s_off[SLOTS / 32];  // bit = the mask switches the row off: its entries gather nothing
+    __shared__ uint32_t s_off[SLOTS / 32 + (CODEW ? 1 : 0)];  // bit = the mask switches the row off: its entries gather nothing (CODEW: + the padding slot's word)
     __shared__ uint32_t s_has[SLOTS / 32];  // bit = the row received a product
     __shared__ uint32_t s_dict[sizeof(T) == 4 ? 256 : 1];  // (ct_mode 2: the 256 bit patterns of the value dictionary)
     const int monoid = MONOID_CT >= 0 ? MONOID_CT : a.monoid;
@@ -134,9 +151,12 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
     W *tl = (W *)a.tl_val;
     const W ident = pull_seed<T, W>(a, monoid);
     // (round 6, PullArgs::ct_mode: packed words -- slot << 19 | column - range base -- in tiles of CT_PACK_SLOTS slots; mode 2: one-byte value codes)
-    const int packed = a.ct_mode;
+    const int packed = CODEW ? 0 : a.ct_mode;
     const int slots_rt = packed ? (CT_PACK_SLOTS < SLOTS ? CT_PACK_SLOTS : SLOTS) : SLOTS;
-    if constexpr (sizeof(T) == 4) {
+    if constexpr (CODEW) {  // (256 loads in flight at once; the barrier behind the first tile's set-up covers them)
+        for (int i = threadIdx.x; i < 256; i += CT_BLOCK) s_dict[i] = ((const uint32_t *)a.vdict)[i];
+        if (threadIdx.x == 0) s_off[SLOTS / 32] = ~0u;
+    } else if constexpr (sizeof(T) == 4) {
         if (packed == 2) {
             for (int i = threadIdx.x; i < 256; i += CT_BLOCK) s_dict[i] = ((const uint32_t *)a.vdict)[i];
             __syncthreads();
@@ -169,6 +189,7 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
             const int64_t ub = ub0 + threadIdx.x;
             int creg[UB][EPL], rk[UB][EPL], cc[UB][EPL];
             T vreg[UB][EPL];
+            unsigned vcode[UB][EPL];  // (CODEW: the entries' dictionary codes)
             bool uv[UB];
 #pragma unroll
             for (int k = 0; k < UB; k++) {
@@ -177,7 +198,16 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
                 const int64_t e = (uv[k] ? u : u_end - 1) * EPL;
                 const uint4 c4 = ptr_stream_x4(tcol + e, snt);
                 creg[k][0] = (int)c4.x; creg[k][1] = (int)c4.y; creg[k][2] = (int)c4.z; creg[k][3] = (int)c4.w;
-                if (packed) {  // (uniform: the row slot above the column's offset in the tile's range; the all-ones word is padding)
+                if constexpr (CODEW) {  // (the slots as in mode 0; the column in the low 24 bits, the value code above it)
+                    const uint2 l2 = ptr_stream_x2(tloc + e, snt);
+                    rk[k][0] = (int)(l2.x & 0xffffu); rk[k][1] = (int)(l2.x >> 16); rk[k][2] = (int)(l2.y & 0xffffu); rk[k][3] = (int)(l2.y >> 16);
+#pragma unroll
+                    for (int i = 0; i < EPL; i++) {
+                        const unsigned w = (unsigned)creg[k][i];
+                        creg[k][i] = (int)(w & 0x00ffffffu);
+                        vcode[k][i] = w >> 24;  // (looked up behind the gathers' issue: the LDS reads travel under them)
+                    }
+                } else if (packed) {  // (uniform: the row slot above the column's offset in the tile's range; the all-ones word is padding)
 #pragma unroll
                     for (int i = 0; i < EPL; i++) {
                         const unsigned w = (unsigned)creg[k][i];
@@ -189,8 +219,8 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
                     const uint2 l2 = ptr_stream_x2(tloc + e, snt);
                     rk[k][0] = (int)(l2.x & 0xffffu); rk[k][1] = (int)(l2.x >> 16); rk[k][2] = (int)(l2.y & 0xffffu); rk[k][3] = (int)(l2.y >> 16);
                 }
-                bool vals_done = false;
-                if constexpr (sizeof(T) == 4) {
+                bool vals_done = CODEW;
+                if constexpr (sizeof(T) == 4 && !CODEW) {
                     if (stage_vals && packed == 2) {  // (one-byte codes, four per unit: the values from the dictionary in LDS)
                         const uint32_t cd = ((const uint32_t *)tval)[uv[k] ? u : u_end - 1];
 #pragma unroll
@@ -275,6 +305,12 @@ __global__ __launch_bounds__(CT_BLOCK) void k_mxv_ctile(const PullArgs a)
                 for (int k = 0; k < UB; k++)
 #pragma unroll
                     for (int i = 0; i < EPL; i++) xv[k][i] = (T)0;
+            }
+            if constexpr (CODEW) {  // (one LDS read per entry: the value of its code)
+#pragma unroll
+                for (int k = 0; k < UB; k++)
+#pragma unroll
+                    for (int i = 0; i < EPL; i++) vreg[k][i] = stage_vals ? __builtin_bit_cast(T, s_dict[vcode[k][i]]) : iso_v;
             }
             // ---- every present product to its row's LDS accumulator: one native LDS atomic -------------------------------------
 #pragma unroll
