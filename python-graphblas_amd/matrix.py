@@ -18,6 +18,27 @@ from .vector import Vector, _iptr, _name_counter, _ptr
 GrB_CSR_FORMAT, GrB_CSC_FORMAT = 0, 1
 
 
+def _cast_scalar(value, np_type):
+    """The GraphBLAS typecast of ONE host number, as the library casts an entry (cast_value, csrc/grb_ops.hpp): to BOOL ``x != 0``;
+    floating point -> integer truncates and saturates, NaN -> 0; integer -> integer wraps.  (numpy's own conversion of 300.7 or NaN to
+    an integer type is undefined, and of an integer beyond the type's range an error.)"""
+    np_type = np.dtype(np_type)
+    v = np.asarray(value)
+    if np_type.kind == "b":
+        return np.bool_(bool(v != 0))
+    if np_type.kind not in "iu":
+        with np.errstate(over="ignore"):
+            return np_type.type(value)
+    info = np.iinfo(np_type)
+    if v.dtype.kind == "f":
+        x = float(v)
+        q = 0 if x != x else (int(info.min) if x <= float(info.min) else (int(info.max) if x >= float(info.max) else int(x)))
+    else:
+        q = int(v) % (1 << info.bits)
+        q -= (1 << info.bits) if q > info.max else 0
+    return np_type.type(q)
+
+
 def _owned_copy(arr):
     """A malloc'd copy of a numpy array: the GxB import / pack entries take OWNERSHIP of their host arrays and release them with
     the library's deallocator (the reference hands over numpy buffers it has unclaimed, core/ss/matrix.py:1300-1349)."""
@@ -410,7 +431,7 @@ class Matrix(BaseType):
             value = value.value
         if not isinstance(value, (bool, int, float, np.generic)):
             raise TypeError(f"Bad type for arg: {type(value).__name__}")
-        return self.dtype.np_type.type(value)
+        return _cast_scalar(value, self.dtype.np_type)
 
     def remove_element(self, i, j):
         """Delete the entry at (i, j), if there is one (``GrB_Matrix_removeElement``; the reference spells it ``del C[i, j]``).  Costs a
