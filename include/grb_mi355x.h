@@ -299,7 +299,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C) */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C); GxB_Matrix_eWiseUnion: 21 the wavefront merge with defaults (k_mat_ewise_wave<.., DEFS>), 22 one operand empty: the other one through the bound-scalar stream of GrB_apply, and 6 when both are empty; `out_nvals` = nnz(C); GrB_Matrix_diag: 23 (k_diag_fill), GxB_Vector_diag: 24 (k_diag_extract), and 6 for both when the input holds no entry or the diagonal has no position; `tiles` = their wavefronts, `out_nvals` = nnz(C) for GrB_Matrix_diag, -1 (not counted, as for mxv) for GxB_Vector_diag */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */
@@ -498,6 +498,13 @@ GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseAdd_Semiring, GrB_Semiring)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_BinaryOp, GrB_BinaryOp)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_Monoid, GrB_Monoid)
 GRB_DECL_MAT_BINARY(GrB_Matrix_eWiseMult_Semiring, GrB_Semiring)
+/* The union with defaults (SuiteSparse GxB_eWiseUnion; grb_mxm_ewise.inc / grb_vecops.hip): the pattern of T is
+ * the union of the input patterns; with X the operator's type, t = add((X) a, (X) b) where both hold an entry, add((X) a, (X) beta)
+ * where A alone does, add((X) alpha, (X) b) where B alone does; GrB_EQ .. GrB_LE give BOOL.  Then C<Mask, replace> = accum(C, T) as for
+ * eWiseAdd, with the same dimension and domain checks; T0 / T1 transpose A / B.  An empty alpha or beta is GrB_EMPTY_OBJECT; C is
+ * unchanged on every failure. */
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Matrix A, const GrB_Scalar alpha, const GrB_Matrix B, const GrB_Scalar beta, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Vector u, const GrB_Scalar alpha, const GrB_Vector v, const GrB_Scalar beta, const GrB_Descriptor desc);
 /* GrB_kronecker (C API 2.0 section 4.3.11; grb_kron.hip): C<Mask, replace> = accum(C, T), T of shape
  * (ma mb) x (na nb) with T[ia mb + ib, ja nb + jb] = op(A[ia, ja], B[ib, jb]); T0 / T1 transpose A / B; the _Semiring form takes the
  * multiply operator.  na nb > 2^31 - 1 is GrB_NOT_IMPLEMENTED (int32 column indices), a product whose entries or row pointers do not
@@ -527,7 +534,13 @@ GrB_Info GrB_Matrix_reduce_BinaryOp(GrB_Vector w, const GrB_Vector mask, const G
 GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar s, const GrB_BinaryOp accum, const GrB_Monoid monoid, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar s, const GrB_BinaryOp accum, const GrB_Monoid monoid, const GrB_Vector u, const GrB_Descriptor desc);
 GrB_Info GrB_Matrix_removeElement(GrB_Matrix C, GrB_Index i, GrB_Index j);
+/* Diagonals (grb_diag.hip).  GrB_Matrix_diag: a NEW square matrix of order n + |k| in v's type with v on its k-th
+ * diagonal, C(i, i + k) = v(i) for k >= 0, C(i - k, i) = v(i) for k < 0; an order beyond 2^31 - 1 is GrB_NOT_IMPLEMENTED (int32 column
+ * indices).  GxB_Vector_diag: v = the k-th diagonal of the m x n matrix A, cast to v's type, v(i) = A(i, i + k) for k >= 0 and
+ * A(i - k, i) for k < 0; v must have that diagonal's length -- min(m, n - k) for k >= 0, min(m + k, n) for k < 0, 0 outside the matrix --,
+ * any other is GrB_DIMENSION_MISMATCH and leaves v as it was; v's old entries are dropped; the descriptor is accepted and ignored. */
 GrB_Info GrB_Matrix_diag(GrB_Matrix *C, const GrB_Vector v, int64_t k);
+GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);
 GrB_Info GrB_Vector_assign_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Scalar s, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc);
 GrB_Info GrB_Vector_setElement_Scalar(GrB_Vector w, const GrB_Scalar s, GrB_Index i);
 GrB_Info GrB_Vector_extractElement_Scalar(GrB_Scalar s, const GrB_Vector u, GrB_Index i);

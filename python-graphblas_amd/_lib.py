@@ -111,6 +111,10 @@ def _declare(L):
         for call in ("eWiseAdd", "eWiseMult"):
             for opclass in ("BinaryOp", "Monoid", "Semiring"):
                 getattr(L, f"GrB_{kind}_{call}_{opclass}").argtypes = [c_void_p] * 7
+    for kind in ("Vector", "Matrix"):  # (C, Mask, accum, add, A, alpha, B, beta, desc)
+        getattr(L, f"GxB_{kind}_eWiseUnion").argtypes = [c_void_p] * 9
+    L.GrB_Matrix_diag.argtypes = [P(c_void_p), c_void_p, ctypes.c_int64]          # (&C, v, k)
+    L.GxB_Vector_diag.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p]  # (v, A, k, desc)
     for opclass in ("BinaryOp", "Monoid", "Semiring"):
         getattr(L, f"GrB_Matrix_kronecker_{opclass}").argtypes = [c_void_p] * 7
     for t, ct in (("BOOL", ctypes.c_bool), ("INT8", ctypes.c_int8), ("INT16", ctypes.c_int16), ("INT32", ctypes.c_int32),

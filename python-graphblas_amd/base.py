@@ -514,6 +514,33 @@ def _scalar_carg(value, what):
     raise TypeError(f"{what}: {type(value).__name__}; expected a number or a Scalar")
 
 
+def union_expression(a, b, op, left_default, right_default, *, kind, output_type, shape, at=False, bt=False):
+    """``a.ewise_union(b, op, left_default, right_default)`` for two Matrices (or transposed views) or two Vectors (reference
+    core/matrix.py:2043-2200, core/vector.py:1150-1290): the delayed call of ``GxB_<kind>_eWiseUnion``.  Both defaults are required, each
+    a number (a Python ``bool`` / ``int`` / ``float`` is BOOL / INT64 / FP64, a numpy scalar its own dtype) or a :class:`Scalar`.  The
+    operator is typed as the reference types it: ``op1`` over ``unify(a.dtype, right_default's dtype)``, ``op2`` over
+    ``unify(left_default's dtype, b.dtype)``, and -- where the two differ -- over the unification of both; operands and defaults are
+    cast to that type.  A Monoid means its binary operator; a Semiring is a ``TypeError``."""
+    from .dtypes import unify
+
+    defaults = []
+    for name, value in (("left_default", left_default), ("right_default", right_default)):
+        if isinstance(value, Scalar):
+            defaults.append(value)
+        elif _is_python_scalar(value):
+            defaults.append(Scalar.from_value(value, name=name))
+        else:
+            raise TypeError(f"Bad type for keyword argument `{name}` in {kind}.ewise_union(...): expected type Scalar, got "
+                            f"{type(value).__name__}.  Literal scalars also accepted.")
+    left, right = defaults
+    top = get_typed_op(op, unify(a.dtype, right.dtype), unify(left.dtype, b.dtype), kind="binary")
+    if top.opclass == "Monoid":
+        top = top.binaryop
+    base_a, base_b = (a._matrix, b._matrix) if kind == "Matrix" else (a, b)
+    return Expression("ewise_union", f"GxB_{kind}_eWiseUnion", [base_a, GrBScalarArg(left), base_b, GrBScalarArg(right)], op=top,
+                      output_type=output_type, shape=shape, at=at, bt=bt)
+
+
 def select_expression(x, op, thunk, *, output_type, shape, at=False):
     """``x.select(op, thunk)`` for a Matrix / TransposedMatrix / Vector ``x`` (reference core/matrix.py:2597-2623, core/vector.py select):
     the delayed call of ``GrB_<kind>_select_<thunk dtype>``, or of the ``_Scalar`` form for a :class:`Scalar` thunk."""

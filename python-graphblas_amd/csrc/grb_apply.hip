@@ -334,6 +334,14 @@ static MatrixOwner apply_build(GB_Matrix_opaque *S, const ApplySpec &sp, int cty
     return Tm;
 }
 
+// T (fresh, type `ctype`) = op(s, S) / op(S, s) for the binary operator `op` of type `ot` (a comparison gives BOOL), for the operations
+// that end in a bound-scalar stream: the union with defaults against an empty operand (matrix_ewise_core, grb_mxm.hip)
+MatrixOwner matrix_apply_bound(GB_Matrix_opaque *S, int op, int ot, bool bind1st, const Thunk &scalar, int ctype, bool full_values)
+{
+    const GB_BinaryOp_opaque bop{op, ot, "eWiseUnion"};
+    return apply_build(S, spec_of_binop(&bop, bind1st, scalar), ctype, full_values);
+}
+
 static void matrix_apply(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, const ApplySpec &sp, GB_Matrix_opaque *A,
                          const GB_Descriptor_opaque *desc)
 {

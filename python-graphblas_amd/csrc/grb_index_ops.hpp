@@ -38,6 +38,10 @@ static inline Thunk thunk_of_scalar(const GB_Scalar_opaque *y, const char *who)
     return t;
 }
 
+// T (fresh storage, type `ctype`) = op(scalar, S) (bind1st) or op(S, scalar) for a binary operator code `op` of type `ot`, by the
+// bound-scalar stream of GrB_apply (grb_apply.hip); full_values: one value per entry even when T could be iso
+MatrixOwner matrix_apply_bound(GB_Matrix_opaque *S, int op, int ot, bool bind1st, const Thunk &scalar, int ctype, bool full_values);
+
 template <int OP> GRB_HD bool sel_pos(int64_t i, int64_t j, int64_t k)
 {
     switch (OP) {

@@ -214,6 +214,7 @@ void preload_extract();
 void preload_apply();
 void preload_assign();
 void preload_kron();
+void preload_diag();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)

@@ -22,6 +22,7 @@
 
 #include "grb_internal.hpp"
 #include "grb_ops.hpp"
+#include "grb_index_ops.hpp"
 
 namespace grb {
 
@@ -2493,9 +2494,11 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
 
 // C<Mask, replace> = accum(C, A (op) B), element-wise over the union (is_add) or the intersection of the patterns (reference
 // core/matrix.py ewise_add / ewise_mult -> GrB_Matrix_eWiseAdd_* / eWiseMult_*); the semantics of ewise_core (grb_vecops.hip), the
-// merge of grb_mxm_ewise.inc.  `op_in` / `ot`: the operator's code and type
+// merge of grb_mxm_ewise.inc.  `op_in` / `ot`: the operator's code and type.  With `alpha` and `beta` (GxB_Matrix_eWiseUnion, is_add;
+// DESIGN.md section 4.12) an entry of A alone is op(a, beta) and an entry of B alone op(alpha, b) instead of passing through
 static void matrix_ewise_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, int op_in, int ot,
-                              GB_Matrix_opaque *A, GB_Matrix_opaque *B, MDesc f, bool is_add)
+                              GB_Matrix_opaque *A, GB_Matrix_opaque *B, MDesc f, bool is_add, const Thunk *alpha = nullptr,
+                              const Thunk *beta = nullptr)
 {
     const uint64_t a_rows = f.t0 ? A->ncols : A->nrows, a_cols = f.t0 ? A->nrows : A->ncols;
     const uint64_t b_rows = f.t1 ? B->ncols : B->nrows, b_cols = f.t1 ? B->nrows : B->ncols;
@@ -2520,13 +2523,27 @@ static void matrix_ewise_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const
         // exact short cuts: the intersection with nothing is empty, the union with nothing a cast copy of the other operand
         ctx().stats.method = 6;
         if (!is_add || (Ae->nvals == 0 && Be->nvals == 0)) Tm.reset(matrix_new(C->type, C->nrows, C->ncols));
-        else Tm = ewise_pass_through(Ae->nvals ? Ae : Be, ot, tt, ctype, Mask || accum);
+        else if (alpha) {
+            // the union with nothing: every entry of the other operand meets the default -- GrB_apply with the scalar bound
+            // second (B empty: op(a, beta)) or first (A empty: op(alpha, b)), one stream over the values
+            Tm = Ae->nvals ? matrix_apply_bound(Ae, op_in, ot, false, *beta, ctype, Mask || accum)
+                           : matrix_apply_bound(Be, op_in, ot, true, *alpha, ctype, Mask || accum);
+            ctx().stats.method = 22;
+        } else Tm = ewise_pass_through(Ae->nvals ? Ae : Be, ot, tt, ctype, Mask || accum);
     } else {
-        ctx().stats.method = 8;
+        ctx().stats.method = alpha ? 21 : 8;
         // operands in the operator's type (an iso operand: its one value)
         DevPtr<char> a_cast, b_cast;
         const void *Ax = values_as(Ae, ot, a_cast), *Bx = values_as(Be, ot, b_cast);
-        Tm = ewise_merge(Ae, Ax, Be, Bx, ot, tt, op, is_add, cmp);
+        alignas(8) unsigned char defs[16] = {0};
+        if (alpha) {  // the defaults in the operator's type
+            GRB_DISPATCH_TYPE(ot, TO, {
+                const TO x = thunk_as<TO>(*alpha), y = thunk_as<TO>(*beta);
+                memcpy(defs, &x, sizeof(TO));
+                memcpy(defs + 8, &y, sizeof(TO));
+            })
+        }
+        Tm = ewise_merge(Ae, Ax, Be, Bx, ot, tt, op, is_add, cmp, nullptr, alpha ? defs : nullptr);
         matrix_retype(Tm.get(), tt, ctype);
     }
     matrix_finish(C, Mask, accum, std::move(Tm), f, C == A || C == B);
@@ -2726,6 +2743,22 @@ GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_BinaryOp, GrB_BinaryOp, op, false)
 GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_Monoid, GrB_Monoid, op, false)
 GRB_MATRIX_EWISE(GrB_Matrix_eWiseMult_Semiring, GrB_Semiring, mult, false)
 #undef GRB_MATRIX_EWISE
+
+// the union with defaults (reference core/matrix.py ewise_union -> GxB_Matrix_eWiseUnion): an empty alpha or beta is GrB_EMPTY_OBJECT
+extern "C" GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Matrix A,
+                                          const GrB_Scalar alpha, const GrB_Matrix B, const GrB_Scalar beta, const GrB_Descriptor desc)
+{
+    GRB_TRY
+    require_init();
+    check_matrix(C, "C");
+    if (Mask) check_matrix(Mask, "Mask");
+    check_matrix(A, "A");
+    check_matrix(B, "B");
+    if (!add) fail(GrB_NULL_POINTER, "eWiseUnion: operator is NULL");
+    const Thunk ta = thunk_of_scalar(alpha, "eWiseUnion (alpha)"), tb = thunk_of_scalar(beta, "eWiseUnion (beta)");
+    matrix_ewise_core(C, Mask, accum, add->op, add->type, A, B, mdesc_of(desc), true, &ta, &tb);
+    GRB_CATCH(errp(C))
+}
 
 namespace grb {
 void preload_mxm() { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_window_offsets_wave)); (void)hipGetLastError(); }

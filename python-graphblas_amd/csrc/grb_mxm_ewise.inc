@@ -14,6 +14,8 @@
 //     -- two popcounts of ballots; no atomics;
 //   * counts per unit -> one scan -> the same walk fills.
 // An iso operand is read as its single value.  Comparison operators write BOOL (k_ewise_cmp of grb_vecops.hip is the vector precedent).
+// The union WITH DEFAULTS (GxB_Matrix_eWiseUnion; DESIGN.md section 4.12) is the same walk and the same count: only the fill differs --
+// an entry of A alone is op(a, beta), an entry of B alone op(alpha, b), where eWiseAdd passes a and b through.
 // LDS: 2 column chunks + 1 value chunk per wavefront = 2 KiB + 256 sizeof(T) per workgroup (k_mat_write_wave: 3 KiB + 256 sizeof(T)).
 #pragma once
 
@@ -41,6 +43,8 @@ struct EwiseArgs {
     const int32_t *rinv;
     const unsigned long long *jbits;
     int jlo, jhi;
+    // DEFS kernels (GxB_Matrix_eWiseUnion): the value that stands in for the absent A entry / B entry, in the operator's type
+    alignas(8) unsigned char alpha[8], beta[8];
 };
 
 template <typename T>
@@ -57,8 +61,8 @@ __device__ __forceinline__ bool ewise_compare(int op, T a, T b)
 }
 
 // T: the operator's type (both operands are in it); CMP: `op` is a comparison and the result BOOL; REGION: the assign flavour of the
-// union (EwiseArgs::rinv)
-template <typename T, bool UNION, bool FILL, bool CMP, bool REGION = false>
+// union (EwiseArgs::rinv); DEFS: the union with defaults (EwiseArgs::alpha / beta; fill pass only)
+template <typename T, bool UNION, bool FILL, bool CMP, bool REGION = false, bool DEFS = false>
 __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
 {
     using TO = typename std::conditional<CMP, bool, T>::type;
@@ -85,6 +89,11 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
     int *sa = s_a[wv], *sb = s_b[wv];
     T *sbv = s_bv[wv];
     const int op = a.op;
+    T alpha = (T)0, beta = (T)0;
+    if constexpr (DEFS) {
+        __builtin_memcpy(&alpha, a.alpha, sizeof(T));
+        __builtin_memcpy(&beta, a.beta, sizeof(T));
+    }
     bool row_in = false;  // (REGION, wave-uniform) the row is one of the assigned rows
     if constexpr (REGION) row_in = a.rinv ? a.rinv[row] >= 0 : true;
     int64_t out = FILL ? a.uoff[unit] : 0, cnt = 0;
@@ -119,6 +128,9 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
                 if (hb) {
                     if constexpr (CMP) za = ewise_compare<T>(op, av, sbv[lb_b]);
                     else za = apply_binop<T>(op, av, sbv[lb_b]);
+                } else if constexpr (DEFS) {
+                    if constexpr (CMP) za = ewise_compare<T>(op, av, beta);
+                    else za = apply_binop<T>(op, av, beta);
                 } else {
                     za = cast_value<TO, T>(av);
                 }
@@ -128,7 +140,12 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
         if (UNION && use_b) {
             lb_a = chunk_lower_bound(sa, bj);
             emit_b = !(lb_a < 64 && sa[lb_a] == bj);
-            zb = cast_value<TO, T>(bv);
+            if constexpr (DEFS) {
+                if constexpr (CMP) zb = ewise_compare<T>(op, alpha, bv);
+                else zb = apply_binop<T>(op, alpha, bv);
+            } else {
+                zb = cast_value<TO, T>(bv);
+            }
         }
         const unsigned long long e_a = __ballot(emit_a), e_b = __ballot(emit_b);
         if (FILL) {
@@ -153,10 +170,13 @@ __global__ __launch_bounds__(256) void k_mat_ewise_wave(const EwiseArgs a)
 }
 
 template <typename T>
-static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea, bool region = false)
+static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs &ea, bool region = false, bool defs = false)
 {
     const dim3 block(256);
-    if (region) {
+    if (defs) {
+        if (cmp) hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, true, false, true>), grid, block, 0, ctx().stream, ea);
+        else hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, false, false, true>), grid, block, 0, ctx().stream, ea);
+    } else if (region) {
         hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, false, true>), grid, block, 0, ctx().stream, ea);
     } else if (is_add) {
         if (cmp) hipLaunchKernelGGL((k_mat_ewise_wave<T, true, true, true>), grid, block, 0, ctx().stream, ea);
@@ -168,9 +188,10 @@ static void launch_ewise_fill(bool is_add, bool cmp, dim3 grid, const EwiseArgs 
 }
 
 // T (fresh storage, type `tt`) = A (op) B; Ax / Bx: the operands' values in the operator's type `ot` (one value when iso); both
-// operands hold entries (or, an empty one, at least its row pointers).  reg: the assign flavour of the union
+// operands hold entries (or, an empty one, at least its row pointers).  reg: the assign flavour of the union.  defs: the union with
+// defaults -- alpha, then beta, 8 bytes each, in type `ot`
 static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_opaque *B, const void *Bx, int ot, int tt, int op, bool is_add, bool cmp,
-                               const MergeRegion *reg = nullptr)
+                               const MergeRegion *reg = nullptr, const unsigned char *defs = nullptr)
 {
     MatrixOwner Tm(matrix_new(type_of_code(tt), A->nrows, A->ncols));
     const int64_t m = (int64_t)A->nrows;
@@ -179,6 +200,7 @@ static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_op
     ea.Bp = B->d_ptr; ea.Bj = B->d_col; ea.Bx = Bx; ea.b_iso = B->iso ? 1 : 0;
     ea.op = op;
     if (reg) { ea.rinv = reg->rinv; ea.jbits = reg->jbits; ea.jlo = (int)reg->jlo; ea.jhi = (int)reg->jhi; }
+    if (defs) { memcpy(ea.alpha, defs, 8); memcpy(ea.beta, defs + 8, 8); }
     const UnitTable ut = unit_table(ea.Ap, ea.Bp, m, (int64_t)A->ncols);
     if (ut.n_units == 0) {
         ctx().stats.kernel_launches += 2;
@@ -201,7 +223,7 @@ static MatrixOwner ewise_merge(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_op
         Tm->d_col = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)nnzT);
         Tm->d_val = dev_alloc(type_size(tt) * (size_t)nnzT);
         ea.uoff = uoff.p; ea.Tj = Tm->d_col; ea.Tx = Tm->d_val;
-        GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea, reg != nullptr); })
+        GRB_DISPATCH_TYPE(ot, TO, { launch_ewise_fill<TO>(is_add, cmp, grid, ea, reg != nullptr, defs != nullptr); })
         ctx().stats.kernel_launches += 2;
     }
     Tm->nvals = nnzT;

@@ -13,8 +13,9 @@
 //     GrB_Matrix_eWiseAdd_* / eWiseMult_* in all three operator forms: grb_mxm.hip; the vector _Semiring forms: grb_vecops.hip;
 //     GrB_{Matrix,Vector}_apply_{BinaryOp1st,BinaryOp2nd,IndexOp}_{<T>,Scalar}: grb_apply.hip; GrB_Matrix_assign, GrB_Matrix_assign_<T> /
 //     _Scalar, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_setElement_<T> / _Scalar, GrB_Matrix_removeElement: grb_assign.hip;
-//     GrB_Matrix_kronecker_* in all three operator forms: grb_kron.hip.  The unary GrB_Matrix_apply / GrB_Vector_apply stay here: no
-//     kernel implements a unary operator; so do GrB_Matrix_diag and GrB_Matrix_reduce_BinaryOp.)
+//     GrB_Matrix_kronecker_* in all three operator forms: grb_kron.hip; GrB_Matrix_diag / GxB_Vector_diag: grb_diag.hip;
+//     GxB_Matrix_eWiseUnion / GxB_Vector_eWiseUnion: grb_mxm.hip / grb_vecops.hip.  The unary GrB_Matrix_apply / GrB_Vector_apply stay
+//     here: no kernel implements a unary operator; so does GrB_Matrix_reduce_BinaryOp.)
 #include <cstring>
 
 #include "grb_internal.hpp"
@@ -298,7 +299,6 @@ NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Vector, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
-extern "C" GrB_Info GrB_Matrix_diag(GrB_Matrix *, const GrB_Vector, int64_t) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Type_new(GrB_Type *, size_t) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_UnaryOp_new(GrB_UnaryOp *, void *, GrB_Type, GrB_Type) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_BinaryOp_new(GrB_BinaryOp *, void *, GrB_Type, GrB_Type, GrB_Type) { return GrB_NOT_IMPLEMENTED; }

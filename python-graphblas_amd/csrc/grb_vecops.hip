@@ -13,6 +13,7 @@
 
 #include "grb_internal.hpp"
 #include "grb_ops.hpp"
+#include "grb_index_ops.hpp"
 
 namespace grb {
 
@@ -298,10 +299,35 @@ __global__ void k_ewise_cmp(int64_t n, const T *u_val, const uint64_t *u_bits, c
     if (lane == 0 && g < ((n + 63) >> 6)) t_bits[g] = b;
 }
 
+// the union with defaults (GxB_Vector_eWiseUnion): t = op(u, v) where both hold an entry, op(u, beta) where u
+// alone does, op(alpha, v) where v alone does; CMP: `op` is a comparison and t BOOL
+template <typename T, bool CMP>
+__global__ void k_ewise_union(int64_t n, const T *u_val, const uint64_t *u_bits, const T *v_val, const uint64_t *v_bits, int op, T alpha, T beta,
+                              typename std::conditional<CMP, bool, T>::type *t_val, uint64_t *t_bits)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = i >> 6;
+    bool has = false;
+    if (i < n) {
+        const bool hu = u_bits && ((u_bits[g] >> lane) & 1ull), hv = v_bits && ((v_bits[g] >> lane) & 1ull);
+        if (hu || hv) {
+            const T x = hu ? u_val[i] : alpha, y = hv ? v_val[i] : beta;
+            if constexpr (CMP) t_val[i] = apply_cmp<T>(op, x, y);
+            else t_val[i] = apply_binop<T>(op, x, y);
+            has = true;
+        }
+    }
+    const unsigned long long b = __ballot(has);
+    if (lane == 0 && g < ((n + 63) >> 6)) t_bits[g] = b;
+}
+
 // w<mask, replace> = accum(w, u (op) v), element-wise over the union (is_add) or the intersection of the patterns
-// (reference core/vector.py:960-1150 -> GrB_Vector_eWiseAdd_* / eWiseMult_*)
+// (reference core/vector.py:960-1150 -> GrB_Vector_eWiseAdd_* / eWiseMult_*); with `alpha` and `beta` the union with defaults
+// (core/vector.py ewise_union -> GxB_Vector_eWiseUnion)
 static void ewise_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, int op_in, int ot,
-                       GB_Vector_opaque *u, GB_Vector_opaque *v, const GB_Descriptor_opaque *desc, bool is_add)
+                       GB_Vector_opaque *u, GB_Vector_opaque *v, const GB_Descriptor_opaque *desc, bool is_add, const Thunk *alpha = nullptr,
+                       const Thunk *beta = nullptr)
 {
     const VDesc f = vflags(desc);
     if (u->n != v->n) fail(GrB_DIMENSION_MISMATCH, "eWise: input sizes " + std::to_string(u->n) + " and " + std::to_string(v->n) + " differ");
@@ -341,7 +367,17 @@ static void ewise_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bin
     DevBuf<uint64_t> t_bits(bits_words64((uint64_t)n));
     const int64_t threads = (int64_t)bits_words64((uint64_t)n) * 64;
     GRB_DISPATCH_TYPE(ot, T, {
-        if (cmp)
+        if (alpha) {
+            const T x = thunk_as<T>(*alpha), y = thunk_as<T>(*beta);  // the defaults in the operator's type
+            if (cmp)
+                hipLaunchKernelGGL((k_ewise_union<T, true>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx().stream, n, (const T *)uv,
+                                   (const uint64_t *)(u->d_val ? u->d_bits : nullptr), (const T *)vv,
+                                   (const uint64_t *)(v->d_val ? v->d_bits : nullptr), op, x, y, (bool *)t_val.p, t_bits.p);
+            else
+                hipLaunchKernelGGL((k_ewise_union<T, false>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx().stream, n, (const T *)uv,
+                                   (const uint64_t *)(u->d_val ? u->d_bits : nullptr), (const T *)vv,
+                                   (const uint64_t *)(v->d_val ? v->d_bits : nullptr), op, x, y, (T *)t_val.p, t_bits.p);
+        } else if (cmp)
             hipLaunchKernelGGL((k_ewise_cmp<T>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx().stream, n, (const T *)uv,
                                (const uint64_t *)(u->d_val ? u->d_bits : nullptr), (const T *)vv,
                                (const uint64_t *)(v->d_val ? v->d_bits : nullptr), op, is_add ? 1 : 0, (bool *)t_val.p, t_bits.p);
@@ -703,6 +739,22 @@ GRB_EWISE(GrB_Vector_eWiseMult_BinaryOp, GrB_BinaryOp, op, false)
 GRB_EWISE(GrB_Vector_eWiseMult_Monoid, GrB_Monoid, op, false)
 GRB_EWISE(GrB_Vector_eWiseMult_Semiring, GrB_Semiring, mult, false)
 #undef GRB_EWISE
+
+// an empty alpha or beta is GrB_EMPTY_OBJECT, with its text on w
+extern "C" GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Vector u,
+                                          const GrB_Scalar alpha, const GrB_Vector v, const GrB_Scalar beta, const GrB_Descriptor desc)
+{
+    GRB_TRY
+    require_init();
+    check_vector_any(w, "w");
+    if (mask) check_vector_any(mask, "mask");
+    check_vector_any(u, "u");
+    check_vector_any(v, "v");
+    if (!add) fail(GrB_NULL_POINTER, "eWiseUnion: operator is NULL");
+    const Thunk ta = thunk_of_scalar(alpha, "eWiseUnion (alpha)"), tb = thunk_of_scalar(beta, "eWiseUnion (beta)");
+    ewise_core(w, mask, accum, add->op, add->type, u, v, desc, true, &ta, &tb);
+    GRB_CATCH(errp(w))
+}
 
 namespace grb {
 void preload_vecops() { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_remove_element)); (void)hipGetLastError(); }

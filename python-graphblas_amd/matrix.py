@@ -350,6 +350,18 @@ class Matrix(BaseType):
         ``GrB_Matrix_eWiseMult_<opclass>``)."""
         return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
 
+    def ewise_union(self, other, op, left_default, right_default):
+        """``C << A.ewise_union(B, op, left_default, right_default)``: union of the patterns; ``op(a, b)`` where both have an entry,
+        ``op(a, right_default)`` where only A has one, ``op(left_default, b)`` where only B has one -- sparse subtraction is
+        ``A.ewise_union(B, binary.minus, 0, 0)`` (reference core/matrix.py:2043-2200 -> C ``GxB_Matrix_eWiseUnion``).  Both defaults are
+        required; how they type the operator: :func:`graphblas_amd.base.union_expression`."""
+        return _ewise_union(self, other, op, left_default, right_default)
+
+    def diag(self, k=0, dtype=None, *, name=None):
+        """The k-th diagonal as a new Vector: ``v[i] = A[i, i + k]`` for ``k >= 0``, ``A[i - k, i]`` for ``k < 0``; ``dtype``: the values
+        cast on the device (reference core/matrix.py diag -> C ``GxB_Vector_diag``).  ``k`` may be an int or a Scalar."""
+        return _diag_vector(self, k, dtype, name)
+
     def kronecker(self, other, op=_binary.times):
         """``C << A.kronecker(B, op)``: the Kronecker product, ``C[ia*mb + ib, ja*nb + jb] = op(A[ia, ja], B[ib, jb])`` (reference
         core/matrix.py:2333-2373 -> C ``GrB_Matrix_kronecker_<opclass>``)."""
@@ -477,6 +489,14 @@ class TransposedMatrix:
         """``C << A.ewise_mult(B, op)``: intersection of the patterns (reference core/matrix.py ewise_mult -> C
         ``GrB_Matrix_eWiseMult_<opclass>``)."""
         return _ewise(self, other, op, "ewise_mult", "GrB_Matrix_eWiseMult")
+
+    def ewise_union(self, other, op, left_default, right_default):
+        """``C << A.T.ewise_union(B, op, left_default, right_default)``: the union runs on the transpose (descriptor T0)."""
+        return _ewise_union(self, other, op, left_default, right_default)
+
+    def diag(self, k=0, dtype=None, *, name=None):
+        """The k-th diagonal of the transpose: diagonal ``-k`` of the matrix itself."""
+        return _diag_vector(self, k, dtype, name)
 
     def kronecker(self, other, op=_binary.times):
         """``C << A.T.kronecker(B, op)``: the product runs on the transpose (descriptor T0)."""
@@ -911,6 +931,41 @@ def _ewise(A, B, op, method_name, cfunc):
     if A.shape != B.shape:
         expr._force_library_error()
     return expr
+
+
+def _ewise_union(A, B, op, left_default, right_default):
+    from .base import union_expression
+
+    if not isinstance(B, (Matrix, TransposedMatrix)):
+        raise TypeError(f"Expected type: Matrix; got {type(B).__name__}")
+    expr = union_expression(A, B, op, left_default, right_default, kind="Matrix", output_type=Matrix, shape=A.shape,
+                            at=A._is_transposed, bt=B._is_transposed)
+    if A.shape != B.shape:
+        expr._force_library_error()
+    return expr
+
+
+def diag_offset(k):
+    """The diagonal number of ``diag(k)``: an int, or a Scalar that holds one (reference tests/test_vector.py:1459-1490)."""
+    from .base import Scalar
+
+    if isinstance(k, Scalar):
+        if k.is_empty:
+            raise ValueError("diag: k is an empty Scalar")
+        k = k.value
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"diag: k must be an integer or a Scalar that holds one; got {type(k).__name__}")
+    return int(k)
+
+
+def _diag_vector(A, k, dtype, name):
+    base = A._matrix
+    k = -diag_offset(k) if A._is_transposed else diag_offset(k)
+    m, n = base._nrows, base._ncols
+    size = min(m, n - k) if 0 <= k < n else (min(m + k, n) if -m < k < 0 else 0)
+    v = Vector(base.dtype if dtype is None else dtype, size, name=name)
+    call("GxB_Vector_diag", [v, base, ctypes.c_int64(k), None])
+    return v
 
 
 def _kronecker(A, B, op):

@@ -362,6 +362,33 @@ class Vector(BaseType):
 
         return self._ewise(other, op if op is not None else _binary.times, "ewise_mult", "GrB_Vector_eWiseMult")
 
+    def ewise_union(self, other, op, left_default, right_default):
+        """``w << u.ewise_union(v, op, left_default, right_default)``: union of the patterns; ``op(u, v)`` where both have an entry,
+        ``op(u, right_default)`` where only u has one, ``op(left_default, v)`` where only v has one (reference core/vector.py:1150-1290
+        -> C ``GxB_Vector_eWiseUnion``).  Both defaults are required; how they type the operator:
+        :func:`graphblas_amd.base.union_expression`."""
+        from .base import union_expression
+
+        if not isinstance(other, Vector):
+            raise TypeError(f"Expected type: Vector; got {type(other).__name__}")
+        expr = union_expression(self, other, op, left_default, right_default, kind="Vector", output_type=Vector, shape=(self._size,))
+        if self._size != other._size:
+            expr._force_library_error()
+        return expr
+
+    def diag(self, k=0, *, name=None):
+        """A new square Matrix of order ``size + |k|`` with this vector on its k-th diagonal: ``C[i, i + k] = v[i]`` for ``k >= 0``,
+        ``C[i - k, i] = v[i]`` for ``k < 0`` (reference core/vector.py diag -> C ``GrB_Matrix_diag``).  ``k`` may be an int or a Scalar."""
+        from .matrix import Matrix, diag_offset
+
+        k = diag_offset(k)
+        C = Matrix.__new__(Matrix)
+        order = self._size + abs(k)
+        C.dtype, C._nrows, C._ncols, C.name = self.dtype, order, order, name or f"M_{next(_name_counter)}"
+        C._handle = ctypes.c_void_p()
+        call_on(self, "GrB_Matrix_diag", [ctypes.byref(C._handle), self._handle, ctypes.c_int64(k)])
+        return C
+
     def select(self, op, thunk=None):
         """``w << v.select("==", 1)`` / ``v.select("index<=", 3)`` / ``v.select(m.V)`` (reference core/vector.py select -> C
         ``GrB_Vector_select_<T>``).  A vector is a column: its index is the row."""
