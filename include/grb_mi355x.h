@@ -223,6 +223,20 @@ extern GrB_Semiring GxB_LOR_LOR_BOOL, GxB_LAND_LAND_BOOL, GxB_LOR_FIRST_BOOL, Gx
     GxB_LAND_FIRST_BOOL, GxB_LAND_SECOND_BOOL, GxB_LOR_LXOR_BOOL, GxB_LAND_LXOR_BOOL, GxB_LXOR_LOR_BOOL,
     GxB_LXOR_LXOR_BOOL, GxB_LXOR_FIRST_BOOL, GxB_LXOR_SECOND_BOOL, GxB_LXOR_PAIR_BOOL;
 
+/* Positional operators, INT32 and INT64: z = mult(A(i,k), B(k,j)) is FIRSTI = i, FIRSTJ = SECONDI = k, SECONDJ = j, the ...1 forms
+ * one more; operand VALUES are never read.  They are implemented as the multiply of the MIN / MAX / ANY / PLUS semirings below, by
+ * GrB_mxv (u is an n x 1 column: FIRSTI = the output index, FIRSTJ = SECONDI = the inner index, SECONDJ = 0) and GrB_vxm (u' is a
+ * 1 x n row: FIRSTI = 0, FIRSTJ = SECONDI = the inner index, SECONDJ = the output index), indices those of the operands as
+ * multiplied (after T0 / T1): the BFS parent step is q<!parent, replace> = q' ANY.SECONDI A.  Every other consumer of an operator
+ * -- mxm, the element-wise operations, apply, kronecker, build, reduce, an accumulator -- answers GrB_NOT_IMPLEMENTED. */
+#define GRB_FOR_EACH_POSITIONAL(X) X(FIRSTI) X(FIRSTI1) X(FIRSTJ) X(FIRSTJ1) X(SECONDI) X(SECONDI1) X(SECONDJ) X(SECONDJ1)
+#define GRB_DECL_POSITIONAL(P)                                                                                         \
+    extern GrB_BinaryOp GxB_##P##_INT32, GxB_##P##_INT64;                                                              \
+    extern GrB_Semiring GxB_MIN_##P##_INT32, GxB_MIN_##P##_INT64, GxB_MAX_##P##_INT32, GxB_MAX_##P##_INT64,            \
+        GxB_ANY_##P##_INT32, GxB_ANY_##P##_INT64, GxB_PLUS_##P##_INT32, GxB_PLUS_##P##_INT64;
+GRB_FOR_EACH_POSITIONAL(GRB_DECL_POSITIONAL)
+#undef GRB_DECL_POSITIONAL
+
 /* =================================================================================================
  * GrX_* : extensions of this library (no reference counterpart).
  * ================================================================================================= */
@@ -299,7 +313,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C); GxB_Matrix_eWiseUnion: 21 the wavefront merge with defaults (k_mat_ewise_wave<.., DEFS>), 22 one operand empty: the other one through the bound-scalar stream of GrB_apply, and 6 when both are empty; `out_nvals` = nnz(C); GrB_Matrix_diag: 23 (k_diag_fill), GxB_Vector_diag: 24 (k_diag_extract), and 6 for both when the input holds no entry or the diagonal has no position; `tiles` = their wavefronts, `out_nvals` = nnz(C) for GrB_Matrix_diag, -1 (not counted, as for mxv) for GxB_Vector_diag */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C); GxB_Matrix_eWiseUnion: 21 the wavefront merge with defaults (k_mat_ewise_wave<.., DEFS>), 22 one operand empty: the other one through the bound-scalar stream of GrB_apply, and 6 when both are empty; `out_nvals` = nnz(C); GrB_Matrix_diag: 23 (k_diag_fill), GxB_Vector_diag: 24 (k_diag_extract), and 6 for both when the input holds no entry or the diagonal has no position; `tiles` = their wavefronts, `out_nvals` = nnz(C) for GrB_Matrix_diag, -1 (not counted, as for mxv) for GxB_Vector_diag; GrB_mxv / GrB_vxm over a positional semiring (GxB_ANY_SECONDI_INT64 ...): 25 the pull kernel (k_posn_pull: a lane group per row), 26 the push kernel (k_posn_push: entry-parallel over the frontier's rows), and 6 when an operand holds no entry; `tiles` = their wavefront units, `flops` = nnz of the matrix pulled over / the entries of the frontier's rows, `out_nvals` = -1 */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */

@@ -122,6 +122,18 @@ DEF_SEMIRING(GxB_LXOR_FIRST_BOOL, OP_LXOR, OP_FIRST, BOOL)
 DEF_SEMIRING(GxB_LXOR_SECOND_BOOL, OP_LXOR, OP_SECOND, BOOL)
 DEF_SEMIRING(GxB_LXOR_PAIR_BOOL, OP_LXOR, OP_PAIR, BOOL)
 
+// ---- positional operators and their semirings (INT32 / INT64; the TIMES_* semirings are not offered) -------------------------
+#define DEF_POSITIONAL(P, T)                                           \
+    DEF_BINOP(GxB_##P##_##T, POS_##P, T)                               \
+    DEF_SEMIRING(GxB_MIN_##P##_##T, OP_MIN, POS_##P, T)                \
+    DEF_SEMIRING(GxB_MAX_##P##_##T, OP_MAX, POS_##P, T)                \
+    DEF_SEMIRING(GxB_ANY_##P##_##T, OP_ANY, POS_##P, T)                \
+    DEF_SEMIRING(GxB_PLUS_##P##_##T, OP_PLUS, POS_##P, T)
+#define DEF_POSITIONAL_T(P) DEF_POSITIONAL(P, INT32) DEF_POSITIONAL(P, INT64)
+GRB_FOR_EACH_POSITIONAL(DEF_POSITIONAL_T)
+#undef DEF_POSITIONAL_T
+#undef DEF_POSITIONAL
+
 // ---- descriptors: GrB_DESC_[R][S][C][T0][T1] ---------------------------------------------------------------
 #define DEF_DESC(SYM, r, s, c, t0, t1)                                     \
     static GB_Descriptor_opaque desc_obj_##SYM = {r, c, s, t0, t1, true};  \

@@ -49,6 +49,16 @@ inline bool sel_is_value(int op) { return op >= SEL_VALUEEQ && op <= SEL_VALUELE
 // ... and the ones that return an index (GrB_apply alone; grb_apply.hip) the range beside it: GrB_select rejects them (check_select_op)
 enum ApplyOp : int { APPLY_ROWINDEX = 3000, APPLY_COLINDEX, APPLY_DIAGINDEX };
 inline bool op_is_apply_index(int op) { return op >= APPLY_ROWINDEX && op <= APPLY_DIAGINDEX; }
+// the positional multiply operators (GxB_FIRSTI .. GxB_SECONDJ1; grb_mxv_posn.hip) a range of their own again: z = mult(A(i,k), B(k,j)) is
+// firsti = i, firstj = secondi = k, secondj = j, the ...1 forms one more (code & 1).  Only the semirings of GrB_mxv / GrB_vxm take them;
+// canonical_op rejects them everywhere else
+enum PosOp : int { POS_FIRSTI = 4000, POS_FIRSTI1, POS_FIRSTJ, POS_FIRSTJ1, POS_SECONDI, POS_SECONDI1, POS_SECONDJ, POS_SECONDJ1 };
+inline bool op_is_positional(int op) { return op >= POS_FIRSTI && op <= POS_SECONDJ1; }
+inline const char *pos_op_name(int op)
+{
+    static const char *const names[8] = {"GxB_FIRSTI", "GxB_FIRSTI1", "GxB_FIRSTJ", "GxB_FIRSTJ1", "GxB_SECONDI", "GxB_SECONDI1", "GxB_SECONDJ", "GxB_SECONDJ1"};
+    return op_is_positional(op) ? names[op - POS_FIRSTI] : "";
+}
 constexpr uint64_t MAGIC_SCALAR = 0x4752425343414c52ULL;  // "GRBSCALR"
 
 constexpr uint64_t MAGIC_VECTOR = 0x4752425645435452ULL;  // "GRBVECTR"
@@ -215,6 +225,7 @@ void preload_apply();
 void preload_assign();
 void preload_kron();
 void preload_diag();
+void preload_mxv_posn();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)
@@ -628,6 +639,11 @@ bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MD
 // C<Mask, replace> = accum(C, T) for T in C's type; T is released on every way out.  c_is_an_input: C is also an operand, whose
 // cached layouts go before the write rule
 void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input);
+
+// ---- GrB_mxv / GrB_vxm over a semiring whose multiply is positional (grb_mxv_posn.hip) ----
+// w<mask> = accum(w, A (+.pos) u)  (vxm: u' (+.pos) A), t0 / t1 as in the two entry points; the vectors are brought to natural order
+void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
+                    GB_Matrix_opaque *A, GB_Vector_opaque *u, bool vxm, MDesc f);
 
 // ---- the region merge of GrB_assign (grb_mxm_ewise.inc) ----
 struct MergeRegion {

@@ -2303,7 +2303,9 @@ extern "C" GrB_Info GrB_mxv(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
     // pull over S = A (or A' with T0); push needs the matrix whose ROWS are indexed like u: S' -- only when cached
     GB_Matrix_opaque *P = f.t0 ? A : A->tr;
     const bool dims_ok = (f.t0 ? A->nrows : A->ncols) == u->n && (f.t0 ? A->ncols : A->nrows) == w->n && (!mask || mask->n == w->n);
-    if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/true, f)) {
+    if (op_is_positional(semiring->mult)) {  // (reads indices, not values: kernels of its own on the plain CSR arrays, grb_mxv_posn.hip)
+        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/false, mdesc_of(desc));
+    } else if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/true, f)) {
     } else {
         GB_Matrix_opaque *S = f.t0 ? matrix_transpose_cached(A) : A;
         mxv_any_order(w, mask, accum, semiring, S, u, /*flip=*/false, f);
@@ -2326,7 +2328,9 @@ extern "C" GrB_Info GrB_vxm(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
     // push walks the rows of P = A (or A' with T1, when cached) selected by u; pull gathers over S = P'
     GB_Matrix_opaque *P = f.t1 ? A->tr : A;
     const bool dims_ok = (f.t1 ? A->ncols : A->nrows) == u->n && (f.t1 ? A->nrows : A->ncols) == w->n && (!mask || mask->n == w->n);
-    if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/false, f)) {
+    if (op_is_positional(semiring->mult)) {
+        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/true, mdesc_of(desc));
+    } else if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/false, f)) {
     } else {
         GB_Matrix_opaque *S = f.t1 ? A : matrix_transpose_cached(A);
         mxv_any_order(w, mask, accum, semiring, S, u, /*flip=*/true, f);

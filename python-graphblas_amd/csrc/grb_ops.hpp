@@ -133,6 +133,8 @@ GRB_HD bool monoid_is_terminal(int op, T v)
 
 inline int canonical_op(int type, int op)
 {
+    if (op_is_positional(op))
+        fail(GrB_NOT_IMPLEMENTED, std::string("the positional operator ") + pos_op_name(op) + " is implemented as the multiply of a GrB_mxv / GrB_vxm semiring only");
     if (op >= OP_UNSUPPORTED) fail(GrB_NOT_IMPLEMENTED, "this builtin operator is not implemented by libgrb_mi355x (handle-only: import-time surface)");
     if (type != TC_BOOL) return op;
     switch (op) {

@@ -5,7 +5,9 @@
 // point per operation.  This file makes those names exist:
 //   * builtin unary, index-unary and the remaining binary operators as DATA symbols.  The kernels implement none of the unary and
 //     extra binary ones: every entry point that consumes an operator goes through canonical_op(), which rejects their codes with
-//     GrB_NOT_IMPLEMENTED.  The index-unary operators that return BOOL (GrB_TRIL ... GrB_ROWGT, GrB_VALUE*_<T>) carry the SelOp
+//     GrB_NOT_IMPLEMENTED.  (The positional BINARY operators GxB_FIRSTI .. GxB_SECONDJ1 and their semirings are no part of this surface: they
+//     live in grb_globals.hip with codes of their own, GrB_mxv / GrB_vxm implement them -- grb_mxv_posn.hip -- and canonical_op names them
+//     when it rejects them anywhere else.)  The index-unary operators that return BOOL (GrB_TRIL ... GrB_ROWGT, GrB_VALUE*_<T>) carry the SelOp
 //     codes GrB_select runs on (grb_select.hip); GrB_ROWINDEX / COLINDEX / DIAGINDEX_* carry the ApplyOp codes of GrB_apply (grb_apply.hip);
 //   * GrB_Scalar for real (a host-side value + presence: the reference passes scalars by GrB_Scalar handle in C API 2.0 calls);
 //   * the entry points of the operations this library does not accelerate, with their C API 2.0 signatures, returning
@@ -295,7 +297,12 @@ static GrB_Info not_impl(GB_Vector_opaque *w, const char *fn)
 
 NI_V(GrB_Vector_apply, const GrB_Vector, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Vector, const GrB_Descriptor)
 NI_M(GrB_Matrix_apply, const GrB_Matrix, const GrB_BinaryOp, const GrB_UnaryOp, const GrB_Matrix, const GrB_Descriptor)
-NI_V(GrB_Matrix_reduce_BinaryOp, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Descriptor)
+extern "C" GrB_Info GrB_Matrix_reduce_BinaryOp(GrB_Vector w, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp op, const GrB_Matrix, const GrB_Descriptor)
+{
+    const GrB_Info rc = not_impl(w, "GrB_Matrix_reduce_BinaryOp");
+    if (op && op_is_positional(op->op) && w && w->magic == MAGIC_VECTOR) w->err += std::string(" (and the positional operator ") + pos_op_name(op->op) + " is no monoid)";
+    return rc;
+}
 
 extern "C" GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Matrix, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }
 extern "C" GrB_Info GrB_Vector_reduce_Monoid_Scalar(GrB_Scalar, const GrB_BinaryOp, const GrB_Monoid, const GrB_Vector, const GrB_Descriptor) { return GrB_NOT_IMPLEMENTED; }

@@ -7,8 +7,13 @@ Mirrors, for the builtin operators on the mxm/mxv/vxm path only, the reference's
 (semiring.py:538-548, 568-587) and string spellings such as ``"min_plus"`` / ``"+"``
 (tests/test_vector.py:362-368, docs/user_guide/operations.rst:44).  Of the aggregators, the ones that are a monoid
 reduction or one semiring mat-vec (``agg.sum/prod/min/max/all/any/any_value/count/exists``, core/operator/agg.py:356-378) are
-here; user-defined functions, UDTs, composite aggregators and positional ops need a JIT and are outside the path
-(SURVEY.md section 2 #6).
+here; user-defined functions, UDTs and composite aggregators need a JIT and are outside the path.
+
+The positional operators ``binary.firsti, firsti1, firstj, firstj1, secondi, secondi1, secondj, secondj1`` are builtins of the
+reference's backend, and of this library: they exist for INT32 and INT64, are INT64 whatever the operands' dtypes are
+(``semiring.any_secondi["INT32"]`` asks for INT32) and are implemented as the multiply of the ``min_ / max_ / any_ / plus_``
+semirings of ``mxv`` / ``vxm`` -- ``q(~parent.S, replace=True) << q.vxm(A, semiring.any_secondi)`` is the BFS parent step.  Anywhere
+else (``mxm``, the element-wise operations, ``apply``, an accumulator) the library raises ``NotImplementedException``.
 
 ``select`` (alias ``indexunary`` for the same names) holds the builtin index-unary operators that return BOOL -- ``tril, triu, diag,
 offdiag, rowle, rowgt, colle, colgt, indexle, indexgt, valueeq, valuene, valuegt, valuege, valuelt, valuele`` -- for
@@ -196,6 +201,30 @@ class Semiring(_OpBase):
         return expr.with_op(self)
 
 
+_POSITIONAL_NAMES = ["firsti", "firsti1", "firstj", "firstj1", "secondi", "secondi1", "secondj", "secondj1"]
+_POSITIONAL_MONOIDS = ["min", "max", "any", "plus"]  # (the reference's backend also has times_*: not offered here)
+
+
+class _PositionalTyping:
+    """Typing of the positional operators: INT32 when asked for by name, INT64 for every other dtype (the operands' values are never
+    read, so their dtypes say nothing about the result)."""
+
+    positional_index = True
+
+    def _coerce(self, dtype):
+        return dtype if dtype.name == "INT32" else _INT64
+
+
+class PositionalBinaryOp(_PositionalTyping, BinaryOp):
+    def _gb_candidates(self, dtype):
+        return [f"GxB_{self.name.upper()}_{dtype.name}"]
+
+
+class PositionalSemiring(_PositionalTyping, Semiring):
+    def _gb_candidates(self, dtype):
+        return [f"GxB_{self.monoid.name.upper()}_{self.binaryop.name.upper()}_{dtype.name}"]
+
+
 _SELECT_POSITIONAL = {"tril": "TRIL", "triu": "TRIU", "diag": "DIAG", "offdiag": "OFFDIAG", "rowle": "ROWLE", "rowgt": "ROWGT",
                       "colle": "COLLE", "colgt": "COLGT", "indexle": "ROWLE", "indexgt": "ROWGT"}  # a vector is a column: index = row
 _SELECT_VALUE = ["valueeq", "valuene", "valuegt", "valuege", "valuelt", "valuele"]
@@ -305,6 +334,13 @@ for _m in _MONOID_NAMES:
         _s = Semiring(f"{_m}_{_b}", getattr(monoid, _m), getattr(binary, _b))
         setattr(semiring, _s.name, _s)
         setattr(op, _s.name, _s)
+for _n in _POSITIONAL_NAMES:
+    setattr(binary, _n, PositionalBinaryOp(_n))
+    setattr(op, _n, getattr(binary, _n))
+    for _m in _POSITIONAL_MONOIDS:
+        _s = PositionalSemiring(f"{_m}_{_n}", getattr(monoid, _m), getattr(binary, _n))
+        setattr(semiring, _s.name, _s)
+        setattr(op, _s.name, _s)
 
 
 from .dtypes import INT64 as _INT64  # noqa: E402
@@ -363,6 +399,8 @@ def get_typed_op(op_, dtype, dtype2=None, *, kind=None):
         raise TypeError(f"Expected type: Semiring; got {op_.opclass} `{op_!r}`")
     if kind == "binary" and isinstance(op_, Semiring):
         raise TypeError(f"Expected type: BinaryOp, Monoid; got Semiring `{op_!r}`")
+    if getattr(op_, "positional_index", False):
+        return op_[_INT64]  # (whatever the operands' dtypes are; INT32 only through op["INT32"])
     dtype = lookup_dtype(dtype)
     if dtype2 is not None:
         dtype = unify(dtype, lookup_dtype(dtype2))
