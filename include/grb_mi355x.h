@@ -313,7 +313,7 @@ typedef struct {
     int64_t tiles;            /* merge-path tiles (mxv/vxm) or row bins (mxm) */
     int64_t flops;            /* mxm: sum_k nnz(A(:,k)) nnz(B(k,:)) from the symbolic pass; mxv: nnz(A) */
     int64_t out_nvals;        /* mxm: nnz(T); mxv: -1 (not counted) */
-    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C); GxB_Matrix_eWiseUnion: 21 the wavefront merge with defaults (k_mat_ewise_wave<.., DEFS>), 22 one operand empty: the other one through the bound-scalar stream of GrB_apply, and 6 when both are empty; `out_nvals` = nnz(C); GrB_Matrix_diag: 23 (k_diag_fill), GxB_Vector_diag: 24 (k_diag_extract), and 6 for both when the input holds no entry or the diagonal has no position; `tiles` = their wavefronts, `out_nvals` = nnz(C) for GrB_Matrix_diag, -1 (not counted, as for mxv) for GxB_Vector_diag; GrB_mxv / GrB_vxm over a positional semiring (GxB_ANY_SECONDI_INT64 ...): 25 the pull kernel (k_posn_pull: a lane group per row), 26 the push kernel (k_posn_push: entry-parallel over the frontier's rows), and 6 when an operand holds no entry; `tiles` = their wavefront units, `flops` = nnz of the matrix pulled over / the entries of the frontier's rows, `out_nvals` = -1 */
+    int32_t method;           /* 1 pull SpMV, 2 push (SpMSpV), 3 hash SpGEMM, 4 mask-driven SpGEMM, 5 mxv by row length (PAIR, full operand), 6 empty operand: write rule only, 7 SpGEMM with the complemented mask fused into the product, 8 element-wise matrix merge (GrB_Matrix_eWiseAdd / eWiseMult), GrB_Matrix_extract by its column list: 9 GrB_ALL or a run lo, lo + 1, ... (segment copy), 10 strictly increasing through a column table, 11 strictly increasing through a search in the list, 12 unsorted or repeating (sort), and 6 for its host short cuts (empty result, GrB_ALL x GrB_ALL); `tiles` = its units, `out_nvals` = nnz(A(I, J)); GrB_Matrix_apply_BinaryOp1st / _BinaryOp2nd / _IndexOp: 13 by value (a stream over the values), 14 by position (entry-parallel with the row walk of select), and 6 when no value pass ran (empty input, an iso result computed on the host); `tiles` = its wavefront units, `out_nvals` = nnz(C); GrB_Matrix_assign by its column list: 15 GrB_ALL or a run lo, lo + 1, ... (column + lo), 16 strictly increasing (J[column], order kept), 17 any other list (one sort of row << 32 | column); its scalar forms GrB_Matrix_assign_<T> / _Scalar / GrB_Matrix_setElement: 18 under a non-complemented mask (the mask's true entries inside I x J as the pattern), 19 without a mask or under a complemented one (the dense region rows I x sorted J), and 6 for the short cuts (ni = 0 or nj = 0, GrB_ALL x GrB_ALL without mask and accumulator); `tiles` = the units of the placement / the mask filter / the dense fill, `out_nvals` = nnz(C); GrB_Matrix_kronecker_*: 20 the entry-parallel fill of the product (k_kron_fill), and 6 when no value was computed on the device (an empty operand, an iso product: PAIR, FIRST or ANY of an iso A, SECOND of an iso B, two iso operands); `tiles` = its wavefront units, `out_nvals` = nnz(C); GxB_Matrix_eWiseUnion: 21 the wavefront merge with defaults (k_mat_ewise_wave<.., DEFS>), 22 one operand empty: the other one through the bound-scalar stream of GrB_apply, and 6 when both are empty; `out_nvals` = nnz(C); GrB_Matrix_diag: 23 (k_diag_fill), GxB_Vector_diag: 24 (k_diag_extract), and 6 for both when the input holds no entry or the diagonal has no position; `tiles` = their wavefronts, `out_nvals` = nnz(C) for GrB_Matrix_diag, -1 (not counted, as for mxv) for GxB_Vector_diag; GrB_mxv / GrB_vxm over a positional semiring (GxB_ANY_SECONDI_INT64 ...): 25 the pull kernel (k_posn_pull: a lane group per row), 26 the push kernel (k_posn_push: entry-parallel over the frontier's rows), and 6 when an operand holds no entry; `tiles` = their wavefront units, `flops` = nnz of the matrix pulled over / the entries of the frontier's rows, `out_nvals` = -1; GxB_Matrix_sort: 27, GxB_Vector_sort: 28 (which rows took which path: GrX_sort_last); `out_nvals` = nnz(C) / -1 */
     int32_t fused_epilogue;   /* 1 if mask/accum/replace were applied inside the product kernel (2: by the short-row kernel with the LDS head) */
     int64_t hot_k;            /* mxv/vxm: entries of the hot-column table used by the call (0 = none) */
     int64_t long_entries;     /* mxv/vxm over a split matrix: entries held by the long rows (0 = no split) */
@@ -555,6 +555,26 @@ GrB_Info GrB_Matrix_removeElement(GrB_Matrix C, GrB_Index i, GrB_Index j);
  * any other is GrB_DIMENSION_MISMATCH and leaves v as it was; v's old entries are dropped; the descriptor is accepted and ignored. */
 GrB_Info GrB_Matrix_diag(GrB_Matrix *C, const GrB_Vector v, int64_t k);
 GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);
+/* Sort by value (grb_sort.hip).  GxB_Matrix_sort: C and P have the shape of A; row i of both holds len_i entries at
+ * columns 0 .. len_i - 1, C(i, r) the r-th value of row i of A in the order of op -- GrB_LT_<T> ascending, GrB_GT_<T> descending, values compared
+ * after a cast to T -- stored as the original entry cast to C's type, P(i, r) the column it had in A.  Either output may be NULL, not both
+ * (GrB_NULL_POINTER); P must be INT64 or UINT64 (GrB_DOMAIN_MISMATCH); no mask, no accumulator, no replace: the outputs are overwritten, and
+ * C, P and A may alias one another.  Ties go to the smaller original index under both operators; -0.0 and +0.0 tie; NaNs tie with each other
+ * and come after every number under BOTH operators; every NaN payload and zero sign arrives in C bit for bit.  Any other builtin operator that
+ * returns BOOL is GrB_NOT_IMPLEMENTED, one that does not GrB_DOMAIN_MISMATCH.  GrB_DESC_T0 sorts columnwise: down each column, entries moved to
+ * the top, P holds row indices, the shape stays A's; every other descriptor field is ignored.  GxB_Vector_sort: one segment; w and p have the
+ * size of u, entries at 0 .. nvals - 1, p holds the original indices.
+ * GrX_sort_limits: the longest row each in-core path takes (a lane group of a wavefront / a workgroup's LDS); longer rows take the radix path.
+ * GrX_sort_last: how many rows (the vector form: its one segment) the last sort call sent down the lane groups (rows without entries count
+ * here), the LDS path and the radix path.
+ * GrX_Matrix_reverse_rows: C (A's shape; values cast to C's type) = A with the values of every row in reverse order over the row's own
+ * pattern -- what ss.compactify(reverse=True) runs behind the sort; C may be A.  GrX_Vector_reverse: the same for the entries of a vector. */
+GrB_Info GxB_Matrix_sort(GrB_Matrix C, GrB_Matrix P, GrB_BinaryOp op, const GrB_Matrix A, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, GrB_BinaryOp op, const GrB_Vector u, const GrB_Descriptor desc);
+GrB_Info GrX_sort_limits(int64_t *wave_max, int64_t *lds_max);   /* longest row each in-core path takes */
+GrB_Info GrX_sort_last(int64_t rows_by_path[3]);                 /* rows the last sort call sent down: lane groups / LDS / radix */
+GrB_Info GrX_Matrix_reverse_rows(GrB_Matrix C, const GrB_Matrix A);
+GrB_Info GrX_Vector_reverse(GrB_Vector w, const GrB_Vector u);
 GrB_Info GrB_Vector_assign_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Scalar s, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc);
 GrB_Info GrB_Vector_setElement_Scalar(GrB_Vector w, const GrB_Scalar s, GrB_Index i);
 GrB_Info GrB_Vector_extractElement_Scalar(GrB_Scalar s, const GrB_Vector u, GrB_Index i);

@@ -115,6 +115,12 @@ def _declare(L):
         getattr(L, f"GxB_{kind}_eWiseUnion").argtypes = [c_void_p] * 9
     L.GrB_Matrix_diag.argtypes = [P(c_void_p), c_void_p, ctypes.c_int64]          # (&C, v, k)
     L.GxB_Vector_diag.argtypes = [c_void_p, c_void_p, ctypes.c_int64, c_void_p]  # (v, A, k, desc)
+    L.GxB_Matrix_sort.argtypes = [c_void_p] * 5  # (C, P, op, A, desc)
+    L.GxB_Vector_sort.argtypes = [c_void_p] * 5  # (w, p, op, u, desc)
+    L.GrX_sort_limits.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64)]
+    L.GrX_sort_last.argtypes = [P(ctypes.c_int64)]
+    L.GrX_Matrix_reverse_rows.argtypes = [c_void_p, c_void_p]
+    L.GrX_Vector_reverse.argtypes = [c_void_p, c_void_p]
     for opclass in ("BinaryOp", "Monoid", "Semiring"):
         getattr(L, f"GrB_Matrix_kronecker_{opclass}").argtypes = [c_void_p] * 7
     for t, ct in (("BOOL", ctypes.c_bool), ("INT8", ctypes.c_int8), ("INT16", ctypes.c_int16), ("INT32", ctypes.c_int32),

@@ -379,6 +379,7 @@ extern "C" GrB_Info GrB_init(GrB_Mode mode)
         preload_kron();
         preload_diag();
         preload_mxv_posn();
+        preload_sort();
         preload_stage();  // (the page-locked blocks of h2d / d2h: not inside the first matrix's layout build)
     }
     if (const char *e = getenv("GRB_DEBUG_FLAGS")) c.debug_flags = atoi(e) & DEBUG_FLAGS_MASK;

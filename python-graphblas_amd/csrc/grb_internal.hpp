@@ -226,6 +226,7 @@ void preload_assign();
 void preload_kron();
 void preload_diag();
 void preload_mxv_posn();
+void preload_sort();
 
 template <typename T>
 struct DevPtr {  // owner of a device block: a callee's result, or a member of a cached layout (freed unless released; T may be void)
@@ -660,6 +661,8 @@ void prim_sort_pairs_u64_u32(const uint64_t *keys_in, uint64_t *keys_out, const 
                              int64_t n, int end_bit);
 // (stable; orders by key bits [begin_bit, end_bit) only)
 void prim_sort_pairs_u64_u32_bits(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
+                                  int64_t n, int begin_bit, int end_bit);
+void prim_sort_pairs_u32_u32_bits(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                                   int64_t n, int begin_bit, int end_bit);
 void prim_exclusive_sum_i64(const int64_t *in, int64_t *out, int64_t n);  // in == out allowed
 

@@ -9,8 +9,8 @@
 
 namespace grb {
 
-void prim_sort_pairs_u64_u32_bits(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
-                                  int64_t n, int begin_bit, int end_bit)
+template <typename K>
+static void sort_pairs_bits(const K *keys_in, K *keys_out, const uint32_t *vals_in, uint32_t *vals_out, int64_t n, int begin_bit, int end_bit)
 {
     if (n <= 0) return;
     size_t tmp_bytes = 0;
@@ -19,6 +19,17 @@ void prim_sort_pairs_u64_u32_bits(const uint64_t *keys_in, uint64_t *keys_out, c
     DevBuf<char> tmp(tmp_bytes);
     GRB_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, (unsigned)begin_bit,
                                       (unsigned)end_bit, ctx().stream));
+}
+void prim_sort_pairs_u64_u32_bits(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
+                                  int64_t n, int begin_bit, int end_bit)
+{
+    sort_pairs_bits<uint64_t>(keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit);
+}
+// (the 4-byte keys and the row ordinals of the segmented sort's long rows, grb_sort.hip)
+void prim_sort_pairs_u32_u32_bits(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
+                                  int64_t n, int begin_bit, int end_bit)
+{
+    sort_pairs_bits<uint32_t>(keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit);
 }
 void prim_sort_pairs_u64_u32(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                              int64_t n, int end_bit)

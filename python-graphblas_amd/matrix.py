@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from .base import BaseType, Expression, InfixMatMul, Mask, ScalarExpression, apply_expression, call, call_on, select_expression
+from .descriptor import lookup as descriptor_lookup
 from .dtypes import lookup_dtype
 from .exceptions import DimensionMismatch
 from .operators import binary as _binary, get_typed_op, monoid as _monoid, semiring as _semiring
@@ -58,7 +59,8 @@ class _MatrixSS:
     """``Matrix.ss`` / ``A.ss``: the reference's SuiteSparse namespace (graphblas/core/ss/matrix.py), reduced to the ingress the
     hot path's callers use -- ``import_csr`` (:1139-1237) and ``pack_csr`` (:1239-1277), both through ``_import_csr``
     (:1279-1349) -> ``GxB_Matrix_{import,pack}_CSR``.  Same keyword arguments; ``take_ownership`` is accepted and means nothing
-    here (the matrix lives in HBM: the host arrays are copied once either way, and the caller's numpy arrays are left alone)."""
+    here (the matrix lives in HBM: the host arrays are copied once either way, and the caller's numpy arrays are left alone).
+    On an instance -- also on ``A.T`` -- ``sort`` (:3983-4048 -> ``GxB_Matrix_sort``) and the ``compactify`` by value (:3869-3981) built on it."""
 
     def __init__(self, parent=None):
         self._parent = parent
@@ -114,6 +116,100 @@ class _MatrixSS:
         finally:
             self._release_leftovers(cells)
         return A
+
+    def sort(self, op=_binary.lt, order="rowwise", *, values=True, permutation=True, nthreads=None, **opts):
+        """``C, P = A.ss.sort(op, order)``: the values of every row (``order="columnwise"``: of every column) in the order of ``op`` --
+        ``binary.lt`` / ``"<"`` ascending, ``binary.gt`` / ``">"`` descending --, moved to the left (to the top), and the column (row)
+        index each value had; both have the shape and ``C`` the dtype of ``A``, ``P`` is UINT64.  Ties go to the smaller index, NaNs
+        come last under both operators.  ``values=False`` / ``permutation=False``: that output is ``None`` and is not computed.
+        ``nthreads`` is accepted and ignored.  On ``A.T`` the order flips.  (reference core/ss/matrix.py:3983-4048 -> C
+        ``GxB_Matrix_sort``)"""
+        A = self._require_parent("sort")
+        base = A._matrix
+        top = sort_operator(op, base.dtype)
+        columnwise = (sort_order(order) == "columnwise") != A._is_transposed
+        if not values and not permutation:
+            return None, None
+        descriptor_lookup(**opts)  # (no descriptor option exists beyond the transpose: anything else is the caller's error)
+        C = Matrix(base.dtype, A._nrows, A._ncols, name="Values") if values else None
+        P = Matrix("UINT64", A._nrows, A._ncols, name="Permutation") if permutation else None
+        if A._is_transposed:  # (the sort runs on the stored matrix: its outputs have the stored shape and are turned afterwards)
+            Cs = Matrix(base.dtype, base._nrows, base._ncols) if values else None
+            Ps = Matrix("UINT64", base._nrows, base._ncols) if permutation else None
+        else:
+            Cs, Ps = C, P
+        desc = descriptor_lookup(transpose_first=columnwise)
+        if Cs is not None:
+            call("GxB_Matrix_sort", [Cs, Ps, top, base, desc])
+        else:
+            call_on(Ps, "GxB_Matrix_sort", [None, Ps._carg, top._carg, base._carg, desc._carg if desc is not None else None])
+        if A._is_transposed:
+            for out, stored in ((C, Cs), (P, Ps)):
+                if out is not None:
+                    call("GrB_transpose", [out, None, None, stored, None])
+        return C, P
+
+    def compactify(self, how="first", k=None, order="rowwise", *, reverse=False, asindex=False, name=None):
+        """The ``k`` smallest (``how="smallest"``, ascending) or largest (``"largest"``, descending) values of every row -- column,
+        ``order="columnwise"`` -- moved to the left (top), as a new Matrix with ``k`` columns (rows); ``k=None``: as many as the longest
+        row holds.  ``reverse``: each row's kept values in reverse order; ``asindex``: the column (row) indices of the values instead
+        (UINT64).  Built from :meth:`sort` and ``select("col<=", k - 1)`` on the device (reference core/ss/matrix.py:3869-3981, whose
+        ``"first"``, ``"last"`` and ``"random"`` this library does not have)."""
+        from .exceptions import NotImplementedException
+
+        A = self._require_parent("compactify")
+        how = how.lower()
+        if how not in {"first", "last", "smallest", "largest", "random"}:
+            raise ValueError('`how` argument must be one of: "first", "last", "smallest", "largest", "random"')
+        if how not in {"smallest", "largest"}:
+            raise NotImplementedException(f'compactify(how="{how}") is not implemented: "smallest" and "largest" are')
+        columnwise = sort_order(order) == "columnwise"
+        if k is not None:
+            k = int(k)
+            if k < 0:
+                raise ValueError("k must be non-negative")
+        C, P = self.sort(_binary.lt if how == "smallest" else _binary.gt, order, values=not asindex, permutation=asindex)
+        X = P if asindex else C
+        dim = X._nrows if columnwise else X._ncols
+        if k is not None and k < dim:
+            X = X.select("row<=" if columnwise else "col<=", k - 1).new()
+        if reverse:
+            if columnwise:
+                Y = X.T.new()
+                call("GrX_Matrix_reverse_rows", [Y, Y])
+                X = Y.T.new()
+            else:
+                call("GrX_Matrix_reverse_rows", [X, X])
+        if k is None:  # the longest row: the columns of the compacted matrix that hold an entry
+            k = (X.reduce_rowwise("any") if columnwise else X.reduce_columnwise("any")).new().nvals
+        X.resize(*((k, X._ncols) if columnwise else (X._nrows, k)))
+        if name is not None:
+            X.name = name
+        return X
+
+    def _require_parent(self, what):
+        if self._parent is None:
+            raise TypeError(f"{what} works on a Matrix instance: A.ss.{what}(...)")
+        return self._parent
+
+
+def sort_order(order):
+    """"rowwise" or "columnwise" from the reference's spellings (core/utils.py get_order)."""
+    val = order.lower() if isinstance(order, str) else order
+    if val in {"c", "col", "cols", "column", "columns", "colwise", "columnwise"}:
+        return "columnwise"
+    if val in {"r", "row", "rows", "rowwise"}:
+        return "rowwise"
+    raise ValueError(f"Bad value for order: {order!r}.  Expected 'rowwise', 'columnwise', 'rows', or 'columns', 'row', 'col', 'r', 'c'.")
+
+
+def sort_operator(op, dtype):
+    """The typed binary operator of a sort: a BinaryOp, its string spelling, or a Monoid standing for its binary operator (the way
+    ``apply`` takes them).  Which operators sort is the library's answer (GrB_LT / GrB_GT; DomainMismatch, NotImplementedException)."""
+    top = get_typed_op(op, dtype, kind="binary")
+    if top.opclass == "Monoid":
+        top = top.binaryop
+    return top
 
 
 class _SSAccessor:
@@ -459,6 +555,7 @@ class TransposedMatrix:
 
     _is_transposed = True
     ndim = 2
+    ss = _SSAccessor()  # A.T.ss.sort(...), A.T.ss.compactify(...): the order flips
 
     def __init__(self, matrix):
         self._matrix = matrix

@@ -27,9 +27,78 @@ def _iptr(idx):
     return (idx if idx.size else _EMPTY_INDEX).ctypes.data_as(ctypes.c_void_p)
 
 
+class _VectorSS:
+    """``v.ss``: the reference's SuiteSparse namespace of a Vector (graphblas/core/ss/vector.py), reduced to ``sort`` (:1559-1620 -> C
+    ``GxB_Vector_sort``) and the ``compactify`` (:1453-1557) built on it."""
+
+    def __init__(self, parent=None):
+        self._parent = parent
+
+    def _require_parent(self, what):
+        if self._parent is None:
+            raise TypeError(f"{what} works on a Vector instance: v.ss.{what}(...)")
+        return self._parent
+
+    def sort(self, op="<", *, values=True, permutation=True, nthreads=None, **opts):
+        """``w, p = v.ss.sort(op)``: the values in the order of ``op`` (``binary.lt`` / ``"<"`` ascending, ``binary.gt`` / ``">"``
+        descending) at positions ``0 .. nvals - 1``, and the index each had; both have the size and ``w`` the dtype of ``v``, ``p`` is
+        UINT64.  Ties go to the smaller index, NaNs come last under both operators.  An output that is not asked for is ``None``;
+        ``nthreads`` is accepted and ignored."""
+        from .descriptor import lookup as descriptor_lookup
+
+        v = self._require_parent("sort")
+        top = get_typed_op(op, v.dtype, kind="binary")
+        if top.opclass == "Monoid":
+            top = top.binaryop
+        if not values and not permutation:
+            return None, None
+        descriptor_lookup(**opts)  # (no descriptor option applies: anything given is the caller's error)
+        w = Vector(v.dtype, v._size, name="Values") if values else None
+        p = Vector("UINT64", v._size, name="Permutation") if permutation else None
+        if w is not None:
+            call("GxB_Vector_sort", [w, p, top, v, None])
+        else:
+            call_on(p, "GxB_Vector_sort", [None, p._carg, top._carg, v._carg, None])
+        return w, p
+
+    def compactify(self, how="first", size=None, *, reverse=False, asindex=False, name=None):
+        """The ``size`` smallest (``how="smallest"``, ascending) or largest (``"largest"``, descending) values at positions
+        ``0 .. size - 1`` of a new Vector of that size; ``size=None``: all of them.  ``reverse``: in reverse order; ``asindex``: their
+        indices instead (UINT64).  Built from :meth:`sort` and ``select("index<=", size - 1)`` on the device (the reference's ``"first"``,
+        ``"last"`` and ``"random"`` this library does not have)."""
+        from .exceptions import NotImplementedException
+
+        v = self._require_parent("compactify")
+        how = how.lower()
+        if how not in {"first", "last", "smallest", "largest", "random"}:
+            raise ValueError('`how` argument must be one of: "first", "last", "smallest", "largest", "random"')
+        if how not in {"smallest", "largest"}:
+            raise NotImplementedException(f'compactify(how="{how}") is not implemented: "smallest" and "largest" are')
+        if size is not None:
+            size = int(size)
+            if size < 0:
+                raise ValueError("size must be non-negative")
+        w, p = self.sort("<" if how == "smallest" else ">", values=not asindex, permutation=asindex)
+        x = p if asindex else w
+        if size is not None and size < x._size:
+            x = x.select("index<=", size - 1).new()
+        if reverse:
+            call("GrX_Vector_reverse", [x, x])
+        x.resize(x.nvals if size is None else size)
+        if name is not None:
+            x.name = name
+        return x
+
+
+class _VectorSSAccessor:
+    def __get__(self, obj, objtype=None):
+        return _VectorSS(obj)
+
+
 class Vector(BaseType):
     _grb_kind = "Vector"
     ndim = 1
+    ss = _VectorSSAccessor()  # v.ss.sort(...), v.ss.compactify(...): reference core/ss/vector.py:1453-1620
 
     def __init__(self, dtype=float, size=0, *, name=None):
         self.dtype = lookup_dtype(dtype)
