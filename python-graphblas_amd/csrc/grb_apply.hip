@@ -349,7 +349,7 @@ static void matrix_apply(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_B
     check_matrix(C, "C");
     check_matrix(A, "A");
     if (Mask) check_matrix(Mask, "Mask");
-    const MDesc f = mdesc_of(desc);  // (T1 is ignored: there is no second input)
+    const Desc f = desc_of(desc);  // (T1 is ignored: there is no second input)
     const uint64_t in_rows = f.t0 ? A->ncols : A->nrows, in_cols = f.t0 ? A->nrows : A->ncols;
     if (C->nrows != in_rows || C->ncols != in_cols)
         fail(GrB_DIMENSION_MISMATCH, "GrB_apply: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the input " +
@@ -377,14 +377,10 @@ static void vector_apply(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_B
         check_vector(u, "u");
         if (mask) check_vector(mask, "mask");
     }
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
+    const Desc f = desc_of(desc);
     if (w->n != u->n) fail(GrB_DIMENSION_MISMATCH, "GrB_apply: output size " + std::to_string(w->n) + " does not match the input size " + std::to_string(u->n));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "GrB_apply: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_apply: accum operator type must equal the output type");
-    if (!mask && comp) {
-        if (replace) vector_release_storage(w);
-        return;
-    }
+    check_vector_mask_accum("GrB_apply", w, mask, accum);
+    if (vector_writes_nothing(w, mask, f)) return;
     ctx().stats = GrX_Stats{};
     if (w->n == 0) return;
     if (sp.by_value) {
@@ -397,36 +393,23 @@ static void vector_apply(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_B
     // t: u's presence bits (a copy: the write rule works in place and w may be u), the values in the operator's result type
     DevBuf<uint64_t> t_bits(nwords);
     DevBuf<char> t_val(type_size(tt) * (size_t)n);
-    DevPtr<char> xcast, tcast;
+    DevPtr<char> x_hold, t_hold;
+    DevPtr<uint64_t> m_hold;
     if (!u->d_val) {
         GRB_HIP(hipMemsetAsync(t_bits.p, 0, nwords * 8, ctx().stream));
         GRB_HIP(hipMemsetAsync(t_val.p, 0, type_size(tt) * (size_t)n, ctx().stream));
     } else {
         d2d(t_bits.p, u->d_bits, nwords * 8);
         if (sp.by_value) {
-            const void *xs = u->d_val;
-            if (sp.xtype != u->type->code) {
-                xcast.p = (char *)dev_alloc(type_size(sp.xtype) * (size_t)n);
-                cast_array(sp.xtype, xcast.p, u->type->code, u->d_val, n);
-                xs = xcast.p;
-            }
+            const void *xs = vector_values_as(u->d_val, u->type->code, sp.xtype, n, x_hold);
             GRB_DISPATCH_TYPE(sp.xtype, X, { launch_vapply_val<X>(sp.code, n, xs, t_bits.p, thunk_as<X>(sp.th), t_val.p); })
         } else {
             launch_vapply_pos(sp.code, tt, n, t_bits.p, position_thunk(sp), t_val.p);
         }
         ctx().stats.kernel_launches += 1;
     }
-    const void *tw = t_val.p;
-    if (tt != wt) {  // t in w's type
-        tcast.p = (char *)dev_alloc(w->type->size * (size_t)n);
-        cast_array(wt, tcast.p, tt, t_val.p, n);
-        tw = tcast.p;
-    }
-    DevBuf<uint64_t> mbits(mask ? nwords : 1);
-    if (mask) vector_mask_bits(mask, structure, mbits.p);
-    vector_ensure_storage(w);
-    vector_write_rule(w, tw, t_bits.p, mask ? mbits.p : nullptr, comp, accum ? canonical_op(wt, accum->op) : -1, replace);
-    w->nvals = -1;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
+    vector_finish(w, vector_values_as(t_val.p, tt, wt, n, t_hold), t_bits.p, m_bits, f, accum);
     GRB_HIP(hipGetLastError());
     if (ctx().blocking) sync_stream();
 }

@@ -449,7 +449,7 @@ static MatrixOwner scalar_pattern_mask(GB_Matrix_opaque *C, GB_Matrix_opaque *Ma
 
 // ---- the calls --------------------------------------------------------------------------------------------------------------------------
 // the last two steps of every form: Z = merge(C, S'), C<Mask, replace> = Z
-static void assign_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, GB_Matrix_opaque *Sp, const MergeRegion *reg, MDesc f)
+static void assign_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, GB_Matrix_opaque *Sp, const MergeRegion *reg, Desc f)
 {
     const int op = accum ? canonical_op(C->type->code, accum->op) : (int)OP_SECOND;
     MatrixOwner Z = matrix_merge_region(C, Sp, op, accum ? nullptr : reg);
@@ -459,7 +459,7 @@ static void assign_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_
 }
 
 // Z = C: nothing is assigned, the write rule still runs (replace under a mask still deletes)
-static void assign_nothing(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, MDesc f)
+static void assign_nothing(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, Desc f)
 {
     ctx().stats.method = 6;
     if (Mask) {
@@ -481,7 +481,7 @@ static void matrix_assign(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_
     if (Mask) check_matrix(Mask, "Mask");
     Ih = asg_host_list(Ih, who, "I");
     Jh = asg_host_list(Jh, who, "J");
-    const MDesc f = mdesc_of(desc);
+    const Desc f = desc_of(desc);
     const uint64_t a_rows = f.t0 ? A->ncols : A->nrows, a_cols = f.t0 ? A->nrows : A->ncols;
     const uint64_t want_rows = Ih ? ni : C->nrows, want_cols = Jh ? nj : C->ncols;
     if (a_rows != want_rows || a_cols != want_cols)
@@ -525,7 +525,7 @@ static void matrix_assign_scalar(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, co
     if (Mask) check_matrix(Mask, "Mask");
     Ih = asg_host_list(Ih, who, "I");
     Jh = asg_host_list(Jh, who, "J");
-    const MDesc f = mdesc_of(desc);
+    const Desc f = desc_of(desc);
     check_mask_accum(who, C, Mask, accum);
     if (accum) canonical_op(C->type->code, accum->op);
     ctx().stats = GrX_Stats{};

@@ -484,7 +484,7 @@ static void matrix_extract(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB
     if (Mask) check_matrix(Mask, "Mask");
     I = ext_list(I, "I");
     J = ext_list(J, "J");
-    const MDesc f = mdesc_of(desc);
+    const Desc f = desc_of(desc);
     const uint64_t in_rows = f.t0 ? A->ncols : A->nrows, in_cols = f.t0 ? A->nrows : A->ncols;
     const uint64_t out_rows = I ? ni : in_rows, out_cols = J ? nj : in_cols;
     if (C->nrows != out_rows || C->ncols != out_cols)
@@ -509,20 +509,16 @@ static void col_extract(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bi
     check_matrix(A, "A");
     if (mask) check_vector(mask, "mask");
     I = ext_list(I, "I");
-    const bool row_form = desc && desc->t0;  // t(k) = A(j, I[k]) instead of A(I[k], j)
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
+    const Desc f = desc_of(desc);
+    const bool row_form = f.t0;  // t(k) = A(j, I[k]) instead of A(I[k], j)
     const uint64_t dim = row_form ? A->ncols : A->nrows, jdim = row_form ? A->nrows : A->ncols;
     const uint64_t n = I ? ni : dim;
     if (w->n != n) fail(GrB_DIMENSION_MISMATCH, "GrB_Col_extract: the output has " + std::to_string(w->n) + " elements, the index list selects " + std::to_string(n));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "GrB_Col_extract: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_Col_extract: accum operator type must equal the output type");
+    check_vector_mask_accum("GrB_Col_extract", w, mask, accum);
     if (j >= jdim)
         fail(GrB_INVALID_INDEX, std::string("GrB_Col_extract: ") + (row_form ? "row " : "column ") + std::to_string(j) + " is outside a matrix of " +
                                     std::to_string(A->nrows) + " x " + std::to_string(A->ncols));
-    if (!mask && comp) {
-        if (replace) vector_release_storage(w);
-        return;
-    }
+    if (vector_writes_nothing(w, mask, f)) return;
     ctx().stats = GrX_Stats{};
     if (n == 0) return;
     const int at = A->type->code;
@@ -557,18 +553,10 @@ static void col_extract(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bi
         ctx().stats.kernel_launches += 1;
     }
     if (I) ext_check_flag(oob.p, "GrB_Col_extract");
-    vector_ensure_storage(w);
-    DevPtr<char> tc;
-    const void *tw = t_val.p;
-    if (w->type->code != at) {
-        tc.reset((char *)dev_alloc(w->type->size * (size_t)n));
-        cast_array(w->type->code, tc.p, at, t_val.p, (int64_t)n);
-        tw = tc.p;
-    }
-    DevBuf<uint64_t> mbits(mask ? nwords : 1);
-    if (mask) vector_mask_bits(mask, structure, mbits.p);
-    vector_write_rule(w, tw, t_bits.p, mask ? mbits.p : nullptr, comp, accum ? canonical_op(w->type->code, accum->op) : -1, replace);
-    w->nvals = -1;
+    DevPtr<char> t_hold;
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
+    vector_finish(w, vector_values_as(t_val.p, at, w->type->code, (int64_t)n, t_hold), t_bits.p, m_bits, f, accum);
     GRB_HIP(hipGetLastError());
     sync_stream();
 }

@@ -610,11 +610,7 @@ void matrix_expand_iso(GB_Matrix_opaque *T);
 // `raw_type`, cast to T's type when the two differ.  Takes ownership of the three arrays
 void matrix_adopt(GB_Matrix_opaque *T, int64_t *Tp, int32_t *Tj, void *raw, int raw_type, int64_t kept, bool iso);
 GB_Vector_opaque *vector_cast_copy(GB_Vector_opaque *v, int type);
-// out_bits = present(v) & (structure ? 1 : value != 0)
 void pack_bool_pv(const uint64_t *present, const bool *val, int64_t n, uint32_t *out);  // 2 bits per element: (present, value)
-void vector_mask_bits(GB_Vector_opaque *m, bool structure, uint64_t *out_bits);
-void vector_write_rule(GB_Vector_opaque *w, const void *t_val, const uint64_t *t_bits, const uint64_t *m_bits, bool comp, int accum,
-                       bool replace);  // w<m, replace> = accum(w, t), in place, t of w's type
 void pack_bool_values(const uint64_t *present, const bool *val, int64_t n, uint64_t *out);
 
 // C<Mask, replace> = accum(C, T), T in C's type with sorted rows (grb_mxm.hip); takes T's storage when nothing masks or accumulates
@@ -624,27 +620,49 @@ void matrix_apply_write_rule(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const 
 // ---- the frame of an operation that builds a fresh matrix T and ends in the write rule (grb_mxm.hip) ----
 // In the caller's order: its own shape check, check_mask_accum, matrix_writes_nothing, build T in a MatrixOwner, matrix_finish.  When the
 // statistics are reset, what out_nvals reports and when the stream is synchronised differ between the operations and stay in the caller.
-struct MDesc {
+struct Desc {
     bool replace = false, comp = false, structure = false, t0 = false, t1 = false;
 };
-inline MDesc mdesc_of(const GB_Descriptor_opaque *desc)
+inline Desc desc_of(const GB_Descriptor_opaque *desc)
 {
-    MDesc f;
+    Desc f;
     if (desc) { f.replace = desc->replace; f.comp = desc->comp; f.structure = desc->structure; f.t0 = desc->t0; f.t1 = desc->t1; }
     return f;
 }
 // Mask has C's shape; accum is an operator of C's type and no comparison.  `op` prefixes the error text ("mxm", "GrB_select", ...)
 void check_mask_accum(const char *op, const GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum);
 // the complement of "no mask" allows no position: nothing may be written, and replace empties C.  true: the call is done
-bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MDesc f);
+bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, Desc f);
 // C<Mask, replace> = accum(C, T) for T in C's type; T is released on every way out.  c_is_an_input: C is also an operand, whose
 // cached layouts go before the write rule
-void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input);
+void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, Desc f, bool c_is_an_input);
+
+// ---- the frame of an operation that builds a dense t (n values + presence words) and ends in the vector write rule (grb_object.hip,
+//      vector_finish: grb_mxv_write.inc) ----
+// In the caller's order: its own size checks, check_vector_mask_accum, vector_writes_nothing, the operands in the operator's type
+// (vector_values_as), t, vector_mask_words, t in w's type (vector_values_as again), vector_finish.  When the statistics are reset and what
+// they count, where n == 0 is tested, which vertex order the vectors are brought to and when the stream is synchronised differ between the
+// operations and stay in the caller.
+// mask has w's size; accum is an operator of w's type and no comparison.  `op` prefixes the error text ("eWise", "GrB_select", ...)
+void check_vector_mask_accum(const char *op, const GB_Vector_opaque *w, const GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum);
+// ... and the four checks of GrB_mxv / GrB_vxm, plain and positional: u against the inner, w against the outer dimension of the matrix as
+// multiplied, the mask, the accumulator
+void check_mxv_sizes(uint64_t n_inner, uint64_t n_outer, const GB_Vector_opaque *w, const GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum,
+                     const GB_Vector_opaque *u);
+// the complement of "no mask" allows no position: nothing may be written, and replace empties w.  true: the call is done
+bool vector_writes_nothing(GB_Vector_opaque *w, const GB_Vector_opaque *mask, Desc f);
+// the words present(mask) & (structure ? 1 : value != 0): nullptr without a mask; the mask's own presence words when it is structural, has
+// storage and is not w (the write rule updates w's words while other wavefronts still read the mask's); else a snapshot that `hold` owns
+const uint64_t *vector_mask_words(GB_Vector_opaque *mask, const GB_Vector_opaque *w, bool structure, DevPtr<uint64_t> &hold);
+// n values of type `from` in type `to`: `val` itself when the types match or val is null, else a cast copy that `hold` owns
+const void *vector_values_as(const void *val, int from, int to, int64_t n, DevPtr<char> &hold);
+// w<m_bits (^comp), replace> = accum(w, t) in place, t of w's type (an empty t: t_val = w->d_val over zeroed t_bits); w's count becomes unknown
+void vector_finish(GB_Vector_opaque *w, const void *t_val, const uint64_t *t_bits, const uint64_t *m_bits, Desc f, const GB_BinaryOp_opaque *accum);
 
 // ---- GrB_mxv / GrB_vxm over a semiring whose multiply is positional (grb_mxv_posn.hip) ----
 // w<mask> = accum(w, A (+.pos) u)  (vxm: u' (+.pos) A), t0 / t1 as in the two entry points; the vectors are brought to natural order
 void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                    GB_Matrix_opaque *A, GB_Vector_opaque *u, bool vxm, MDesc f);
+                    GB_Matrix_opaque *A, GB_Vector_opaque *u, bool vxm, Desc f);
 
 // ---- the region merge of GrB_assign (grb_mxm_ewise.inc) ----
 struct MergeRegion {

@@ -199,7 +199,7 @@ static MatrixOwner kron_build(GB_Matrix_opaque *A, GB_Matrix_opaque *B, int code
 static void matrix_kron_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, int op_in, int ot, GB_Matrix_opaque *A,
                              GB_Matrix_opaque *B, const GB_Descriptor_opaque *desc)
 {
-    const MDesc f = mdesc_of(desc);
+    const Desc f = desc_of(desc);
     const uint64_t a_rows = f.t0 ? A->ncols : A->nrows, a_cols = f.t0 ? A->nrows : A->ncols;
     const uint64_t b_rows = f.t1 ? B->ncols : B->nrows, b_cols = f.t1 ? B->nrows : B->ncols;
     uint64_t t_rows = 0, t_cols = 0;

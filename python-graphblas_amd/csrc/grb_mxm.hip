@@ -2015,12 +2015,12 @@ static GB_Matrix_opaque *spgemm(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_o
         DevBuf<int64_t> rownnz(m + 1, true);
         a.row_nnz = rownnz.p;
         // column-window offsets of B's rows (heavy rows walk the windows in both passes): n_B x (windows + 1) int32, per call
-        DevBuf<int32_t> woff(0), wcnt(0), wrow(0), wbm(0);
-        DevBuf<unsigned long long> bm_pool(0), bm_cur(16 * MU_POOLS), class_cnt(MU_CSLOTS * MU_NCLS);
+        DevPtr<int32_t> woff, wcnt, wrow, wbm, cm_woff;
+        DevPtr<unsigned long long> bm_pool;
+        DevBuf<unsigned long long> bm_cur(16 * MU_POOLS), class_cnt(MU_CSLOTS * MU_NCLS);
         std::vector<unsigned long long> class_host(MU_CSLOTS * MU_NCLS);
         const int64_t n_win = ceil_div((int64_t)B->ncols, MM_WIN);
         const int64_t woff_entries = (int64_t)B->nrows * (n_win + 1);
-        DevBuf<int32_t> cm_woff(0);
         bool fuse = forbidden && forbidden->p && !(ctx().debug_flags & 256) && ctx().mxm_heavy_kernel == 1 && n_win < 65536 &&
                     woff_entries * 4 <= (8ll << 30) && m * (n_win + 1) * 4 <= (8ll << 30);
         auto ensure_woff = [&]() {
@@ -2030,8 +2030,7 @@ static GB_Matrix_opaque *spgemm(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_o
                 a.n_win = (int)n_win;
                 return;
             }
-            dev_free(woff.p);
-            woff.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)woff_entries);
+            woff.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)woff_entries));
             launch_window_offsets((const int64_t *)B->d_ptr, (const int32_t *)B->d_col, (int64_t)B->nrows, (int)n_win, woff.p,
                                   (const int32_t *)nullptr, (unsigned long long *)nullptr, UnitLimits{});
             a.woff = woff.p;
@@ -2068,10 +2067,8 @@ static GB_Matrix_opaque *spgemm(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_o
             if (rb.count(4) && units_ok && rb.count(4) * (n_win + 1) * 4 <= (8ll << 30)) {
                 ensure_woff();
                 if (a.woff) {
-                    dev_free(wcnt.p);
-                    wcnt.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(rb.count(4) * (n_win + 1)));
-                    dev_free(wrow.p);
-                    wrow.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)m);
+                    wcnt.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(rb.count(4) * (n_win + 1))));
+                    wrow.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)m));
                     GRB_HIP(hipMemsetAsync(wrow.p, 0xFF, sizeof(int32_t) * (size_t)m, ctx().stream));
                     a.wcnt = wcnt.p;
                     a.wrow = wrow.p;
@@ -2084,10 +2081,8 @@ static GB_Matrix_opaque *spgemm(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_o
                     const int64_t cap = std::min<int64_t>({rb.count(4) * n_win, (int64_t)(ctx().mxm_bitmap_pool_mb << 20) / bm_bytes,
                                                            (int64_t)(free_b / 4) / bm_bytes, ctx().mxm_bitmap_pool_cap});
                     if (cap > 0) {
-                        dev_free(wbm.p);
-                        wbm.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(rb.count(4) * n_win));
-                        dev_free(bm_pool.p);
-                        bm_pool.p = (unsigned long long *)dev_alloc((size_t)(cap * bm_bytes));
+                        wbm.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(rb.count(4) * n_win)));
+                        bm_pool.reset((unsigned long long *)dev_alloc((size_t)(cap * bm_bytes)));
                         GRB_HIP(hipMemsetAsync(bm_cur.p, 0, sizeof(unsigned long long) * 16 * MU_POOLS, ctx().stream));
                         a.wbm = wbm.p;
                         a.bm_pool = bm_pool.p;
@@ -2101,8 +2096,7 @@ static GB_Matrix_opaque *spgemm(GB_Matrix_opaque *A, const void *Ax, GB_Matrix_o
             // the fused complemented mask: every kernel this product will run must know it (the dense-accumulator fall-backs do not)
             fuse = fuse && (rb.count(4) == 0 || (a.woff && a.wrow && a.wcnt));
             if (fuse) {
-                dev_free(cm_woff.p);
-                cm_woff.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(m * (n_win + 1)));
+                cm_woff.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)(m * (n_win + 1))));
                 launch_window_offsets(forbidden->p, forbidden->j, m, (int)n_win, cm_woff.p, (const int32_t *)nullptr,
                                       (unsigned long long *)nullptr, UnitLimits{});
                 a.CMp = forbidden->p;
@@ -2188,7 +2182,8 @@ static GB_Matrix_opaque *spgemm_masked(GB_Matrix_opaque *A, const void *Ax, GB_M
         const bool units_ok = ctx().mxm_heavy_kernel == 1 && !(ctx().debug_flags & 256) && woff_entries * 4 <= (8ll << 30) &&
                               mwoff_entries * 4 <= (8ll << 30) && n_win < 65536 && Mask->ncols == B->ncols &&
                               flops_total >= ctx().mxm_masked_units_min_flops;
-        DevBuf<int32_t> urow(units_ok ? m : 0), mwoff(0);
+        DevBuf<int32_t> urow(units_ok ? m : 0);
+        DevPtr<int32_t> woff, mwoff;
         if (units_ok) {
             const int64_t nnzA = A->nvals;
             DevBuf<int64_t> F(nnzA + 1);
@@ -2200,21 +2195,18 @@ static GB_Matrix_opaque *spgemm_masked(GB_Matrix_opaque *A, const void *Ax, GB_M
         }
         RowBins rb(m);
         make_bins(rb, A->d_ptr, nullptr, m, size.p, 128, 1024, 4096, units_ok ? urow.p : nullptr);
-        DevBuf<int32_t> woff(0);
         if (rb.count(4)) {
             if (woff_entries * 4 > (8ll << 30)) {
                 matrix_free(Tm);
                 return nullptr;
             }
-            dev_free(woff.p);
-            woff.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)woff_entries);
+            woff.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)woff_entries));
             launch_window_offsets((const int64_t *)B->d_ptr, (const int32_t *)B->d_col, (int64_t)B->nrows, (int)n_win, woff.p,
                                   (const int32_t *)nullptr, (unsigned long long *)nullptr, UnitLimits{});
             a.woff = woff.p;
             a.n_win = (int)n_win;
             if (units_ok) {  // the mask rows' window offsets play the part of the symbolic pass's counts, classes counted on the way
-                dev_free(mwoff.p);
-                mwoff.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)mwoff_entries);
+                mwoff.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)mwoff_entries));
                 DevBuf<unsigned long long> ccnt(MU_CSLOTS * MU_NCLS, true);
                 launch_window_offsets(a.Mp, a.Mj, m, (int)n_win, mwoff.p, (const int32_t *)urow.p, ccnt.p, unit_limits(true));
                 std::vector<unsigned long long> known(MU_CSLOTS * MU_NCLS);
@@ -2271,7 +2263,7 @@ __global__ void k_true_cols(const int64_t *pos, const int32_t *Mj, int64_t n, in
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p < n && pos[p + 1] != pos[p]) out[pos[p]] = Mj[p];
 }
-static void true_pattern(GB_Matrix_opaque *Mask, DevBuf<int64_t> &ptr, DevBuf<int32_t> &col)
+static void true_pattern(GB_Matrix_opaque *Mask, DevPtr<int64_t> &ptr, DevPtr<int32_t> &col)
 {
     const int64_t n = Mask->nvals, m = (int64_t)Mask->nrows;
     DevBuf<int64_t> pos(n + 1);
@@ -2292,12 +2284,10 @@ static void true_pattern(GB_Matrix_opaque *Mask, DevBuf<int64_t> &ptr, DevBuf<in
     prim_exclusive_sum_i64(pos.p, pos.p, n + 1);
     int64_t n_true = 0;
     d2h(&n_true, pos.p + n, sizeof(int64_t));
-    dev_free(ptr.p);
-    ptr.p = (int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1));
+    ptr.reset((int64_t *)dev_alloc(sizeof(int64_t) * (size_t)(m + 1)));
     hipLaunchKernelGGL(k_cap_rowptr, dim3((unsigned)ceil_div(m + 1, 256)), dim3(256), 0, ctx().stream, matrix_rowptr(Mask),
                        (const int64_t *)pos.p, m, ptr.p);
-    dev_free(col.p);
-    col.p = (int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(1, n_true));
+    col.reset((int32_t *)dev_alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(1, n_true)));
     hipLaunchKernelGGL(k_true_cols, grid, block, 0, ctx().stream, (const int64_t *)pos.p, (const int32_t *)Mask->d_col, n, col.p);
     ctx().stats.kernel_launches += 3;
     sync_stream();  // (pos is released at the end of this scope)
@@ -2419,21 +2409,21 @@ void check_mask_accum(const char *op, const GB_Matrix_opaque *C, const GB_Matrix
         fail(GrB_DOMAIN_MISMATCH, std::string(op) + ": accum operator type must equal the output type");
 }
 
-bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, MDesc f)
+bool matrix_writes_nothing(GB_Matrix_opaque *C, const GB_Matrix_opaque *Mask, Desc f)
 {
     if (Mask || !f.comp) return false;
     if (f.replace) matrix_release_storage(C);
     return true;
 }
 
-void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, MDesc f, bool c_is_an_input)
+void matrix_finish(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, MatrixOwner T, Desc f, bool c_is_an_input)
 {
     if (c_is_an_input) matrix_invalidate_caches(C);  // (T is a fresh object: C may alias an operand or the mask)
     matrix_apply_write_rule(C, Mask, accum, T.get(), f.replace, f.comp, f.structure);
 }
 
 static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum,
-                     const GB_Semiring_opaque *sr, GB_Matrix_opaque *A, GB_Matrix_opaque *B, MDesc f)
+                     const GB_Semiring_opaque *sr, GB_Matrix_opaque *A, GB_Matrix_opaque *B, Desc f)
 {
     GB_Matrix_opaque *Ae = f.t0 ? matrix_transpose_cached(A) : A;
     GB_Matrix_opaque *Be = f.t1 ? matrix_transpose_cached(B) : B;
@@ -2464,8 +2454,8 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
     // A complemented mask is fused into the product: the positions it forbids never enter T (they would only be dropped by the
     // write rule, after a second pass over all of T)
     bool fused = false;
-    DevBuf<int64_t> fp_ptr(0);
-    DevBuf<int32_t> fp_col(0);
+    DevPtr<int64_t> fp_ptr;
+    DevPtr<int32_t> fp_col;
     if (!Tm && Mask && f.comp && ctx().mxm_mask_mode != 0 && Mask->nvals > 0) {
         ForbiddenPattern fp;
         if (f.structure) {
@@ -2497,7 +2487,7 @@ static void mxm_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_Binar
 // merge of grb_mxm_ewise.inc.  `op_in` / `ot`: the operator's code and type.  With `alpha` and `beta` (GxB_Matrix_eWiseUnion, is_add;
 // DESIGN.md section 4.12) an entry of A alone is op(a, beta) and an entry of B alone op(alpha, b) instead of passing through
 static void matrix_ewise_core(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_BinaryOp_opaque *accum, int op_in, int ot,
-                              GB_Matrix_opaque *A, GB_Matrix_opaque *B, MDesc f, bool is_add, const Thunk *alpha = nullptr,
+                              GB_Matrix_opaque *A, GB_Matrix_opaque *B, Desc f, bool is_add, const Thunk *alpha = nullptr,
                               const Thunk *beta = nullptr)
 {
     const uint64_t a_rows = f.t0 ? A->ncols : A->nrows, a_cols = f.t0 ? A->nrows : A->ncols;
@@ -2717,7 +2707,7 @@ extern "C" GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
     check_matrix(A, "A");
     check_matrix(B, "B");
     if (!semiring) fail(GrB_NULL_POINTER, "semiring is NULL");
-    mxm_core(C, Mask, accum, semiring, A, B, mdesc_of(desc));
+    mxm_core(C, Mask, accum, semiring, A, B, desc_of(desc));
     GRB_CATCH(errp(C))
 }
 
@@ -2733,7 +2723,7 @@ extern "C" GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
         check_matrix(A, "A");                                                                                                     \
         check_matrix(B, "B");                                                                                                     \
         if (!op) fail(GrB_NULL_POINTER, "eWise: operator is NULL");                                                               \
-        matrix_ewise_core(C, Mask, accum, op->CODE, op->type, A, B, mdesc_of(desc), IS_ADD);                                     \
+        matrix_ewise_core(C, Mask, accum, op->CODE, op->type, A, B, desc_of(desc), IS_ADD);                                     \
         GRB_CATCH(errp(C))                                                                                                        \
     }
 GRB_MATRIX_EWISE(GrB_Matrix_eWiseAdd_BinaryOp, GrB_BinaryOp, op, true)
@@ -2756,7 +2746,7 @@ extern "C" GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, c
     check_matrix(B, "B");
     if (!add) fail(GrB_NULL_POINTER, "eWiseUnion: operator is NULL");
     const Thunk ta = thunk_of_scalar(alpha, "eWiseUnion (alpha)"), tb = thunk_of_scalar(beta, "eWiseUnion (beta)");
-    matrix_ewise_core(C, Mask, accum, add->op, add->type, A, B, mdesc_of(desc), true, &ta, &tb);
+    matrix_ewise_core(C, Mask, accum, add->op, add->type, A, B, desc_of(desc), true, &ta, &tb);
     GRB_CATCH(errp(C))
 }
 

@@ -1615,25 +1615,12 @@ static void pull_dispatch(GB_Matrix_opaque *A, int type, PullArgs &a)
     GRB_DISPATCH_TYPE(type, T, { launch_pull<T, -1, -1>(A, a); })
 }
 
-struct DescFlags {
-    bool replace = false, comp = false, structure = false, t0 = false, t1 = false;
-};
-static DescFlags flags_of(const GB_Descriptor_opaque *d)
-{
-    DescFlags f;
-    if (d) { f.replace = d->replace; f.comp = d->comp; f.structure = d->structure; f.t0 = d->t0; f.t1 = d->t1; }
-    return f;
-}
-
 // w<mask> = accum(w, S (+.x) u) where S is the CSR to pull over (A or its cached transpose);
 // `flip` evaluates mult(u_k, S_ik) instead of mult(S_ik, u_k)  (vxm).
 static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum,
-                     const GB_Semiring_opaque *sr, GB_Matrix_opaque *S, GB_Vector_opaque *u, bool flip, DescFlags f)
+                     const GB_Semiring_opaque *sr, GB_Matrix_opaque *S, GB_Vector_opaque *u, bool flip, Desc f)
 {
-    if (S->ncols != u->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: matrix inner dimension " + std::to_string(S->ncols) + " does not match vector size " + std::to_string(u->n));
-    if (w->n != S->nrows) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: output size " + std::to_string(w->n) + " does not match matrix dimension " + std::to_string(S->nrows));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: mask size does not match output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "mxv/vxm: accum operator type must equal the output type");
+    check_mxv_sizes(S->ncols, S->nrows, w, mask, accum, u);
     ctx().stats = GrX_Stats{};
     ctx().stats.method = 1;
     ctx().stats.long_kernel = -1;
@@ -1642,28 +1629,13 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     ctx().stats.out_nvals = -1;
     const int64_t m = (int64_t)w->n;
     if (m == 0) return;
-    if (!mask && f.comp) {  // complement of "no mask": nothing may be written
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    if (vector_writes_nothing(w, mask, f)) return;
     const int st = sr->type;
     const int monoid = canonical_op(st, sr->monoid);
     int mult = canonical_op(st, sr->mult);
     if (flip) mult = flip_op(mult);
-
-    // ---- mask bits ------------------------------------------------------------------------------------------
-    DevBuf<uint64_t> mbits_tmp(0);
-    const uint64_t *m_bits = nullptr;
-    if (mask) {
-        // (a mask that aliases w is snapshotted: tiles update w's presence words while others still read them)
-        if (f.structure && mask->d_val && mask != w) m_bits = mask->d_bits;
-        else {
-            dev_free(mbits_tmp.p);
-            mbits_tmp.p = (uint64_t *)dev_alloc(bits_words64(mask->n) * 8);
-            vector_mask_bits(mask, f.structure, mbits_tmp.p);
-            m_bits = mbits_tmp.p;
-        }
-    }
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
 
     // ---- an operand without entries: T is empty, only the write rule remains (and nothing of the size of u is touched: empty
     //      objects may be as large as GrB_INDEX_MAX + 1) ---------------------------------------------------------------------
@@ -1676,11 +1648,8 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
         }
         vector_ensure_storage(w);
         DevBuf<uint64_t> t_bits(bits_words64(w->n), true);
-        const int acc_op = accum ? canonical_op(w->type->code, accum->op) : -1;
-        vector_write_rule(w, w->d_val, t_bits.p, m_bits, f.comp, acc_op, f.replace);
+        vector_finish(w, w->d_val, t_bits.p, m_bits, f, accum);
         ctx().stats.kernel_launches += 1;
-        ctx().stats.method = 6;
-        w->nvals = -1;
         if (ctx().blocking) sync_stream();
         return;
     }
@@ -1689,26 +1658,13 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     bool need_aval = !(mult == OP_PAIR || mult == OP_SECOND) && S->nvals > 0;
     const bool need_uval = !(mult == OP_PAIR || mult == OP_FIRST || mult == OP_ANY);
     if (mult == OP_ANY) need_aval = S->nvals > 0;
-    DevBuf<char> a_cast(0), u_cast(0);
-    const void *aval = S->d_val;
-    if (need_aval && S->type->code != st) {
-        const int64_t nv = S->iso ? 1 : S->nvals;
-        dev_free(a_cast.p);
-        a_cast.p = (char *)dev_alloc(type_size(st) * (size_t)nv);
-        cast_array(st, a_cast.p, S->type->code, S->d_val, nv);
-        aval = a_cast.p;
-    }
+    DevPtr<char> a_hold, u_hold;
+    const void *aval = need_aval ? values_as(S, st, a_hold) : S->d_val;
     vector_ensure_storage(u);
-    const void *uval = u->d_val;
     // (values nobody reads still travel with the presence image [hot table | u] that is built when u is not full, and that
     //  image is laid out in the semiring's type: only a full operand whose values are unused skips the cast)
     const bool u_full_now = u->nvals == (int64_t)u->n;
-    if ((need_uval || !u_full_now) && u->type->code != st) {
-        dev_free(u_cast.p);
-        u_cast.p = (char *)dev_alloc(type_size(st) * (size_t)u->n);
-        cast_array(st, u_cast.p, u->type->code, u->d_val, (int64_t)u->n);
-        uval = u_cast.p;
-    }
+    const void *uval = (need_uval || !u_full_now) ? vector_values_as(u->d_val, u->type->code, st, (int64_t)u->n, u_hold) : u->d_val;
 
     PullArgs a{};
     a.m = m;
@@ -1734,8 +1690,8 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
         fail(GrB_NOT_IMPLEMENTED, "mxv/vxm: input vectors of 4 GiB or more are not supported by the pull kernel yet");
     // hot-column table (wide matrices with a skewed column-degree distribution): the kernel indexes ONE image
     // [ K hot entries | the n entries of u ] with the re-coded column indices (hot rank, or K + col)
-    DevBuf<char> xcat_val(0);
-    DevBuf<uint64_t> xcat_bits(0);
+    DevPtr<char> xcat_val;
+    DevPtr<uint64_t> xcat_bits;
     // the first pull over a large matrix runs on the CSR arrays as they are; the layouts below (tens of milliseconds to build at
     // scale 24) are built when the matrix comes back for a second product
     const bool lazy = ctx().lazy_layout && S->nvals >= ctx().lazy_min_nnz && S->pull_calls == 0 && S->hot.hot_state == 0 && S->split.split_state == 0;
@@ -1766,12 +1722,10 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
                                        (T *)img_val, img_bits, (int64_t)u->n);
                 })
             } else {
-                dev_free(xcat_val.p);
-                xcat_val.p = (char *)dev_alloc(vb * (size_t)(k + u->n));
-                dev_free(xcat_bits.p);
-                xcat_bits.p = (uint64_t *)dev_alloc((size_t)(k / 64 + bits_words64(u->n)) * 8);
-                img_val = xcat_val.p;
-                img_bits = xcat_bits.p;
+                xcat_val.reset((char *)dev_alloc(vb * (size_t)(k + u->n)));
+                xcat_bits.reset((uint64_t *)dev_alloc((size_t)(k / 64 + bits_words64(u->n)) * 8));
+                img_val = xcat_val.get();
+                img_bits = xcat_bits.get();
                 const int64_t copy_threads = std::max<int64_t>(((int64_t)u->n * (int64_t)vb >> 4) + 1, (int64_t)bits_words64(u->n));
                 if (((uintptr_t)uval & 15u) == 0) {
                     GRB_DISPATCH_TYPE(st, T, {
@@ -1831,13 +1785,12 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     // accumulator leaves the identity iff the row meets a present entry -- the product's pattern is exact -- and the kernels skip the
     // presence gathers and take the fast hot-strip path: the sweeps of an SSSP loop, whose distance vector never becomes full, went from
     // 1.53 to ~0.8 ms (section 4.1.10)
-    DevBuf<char> fill_img(0);
+    DevPtr<char> fill_img;
     // (vals_finite comes with the dictionary, i.e. with FP32 today; the bound on the operand keeps every product finite)
     const double fill_limit = (st == TC_FP32 ? 3.4028234663852886e38 : 1.7976931348623157e308) - S->vd.vals_absmax;
     if (S->hot_identity && !a.u_full && a.need_uval && ctx().fill_absent && S->vd.vals_finite && fill_limit > 0 && !S->iso && (st == TC_FP32 || st == TC_FP64) &&
         mult == OP_PLUS && (monoid == OP_MIN || monoid == OP_MAX) && S->split.split_state == 1 && S->split.split_kind == 4) {
-        dev_free(fill_img.p);
-        fill_img.p = (char *)dev_alloc(type_size(st) * (size_t)u->n);
+        fill_img.reset((char *)dev_alloc(type_size(st) * (size_t)u->n));
         DevBuf<int> flag(1, true);
         if (st == TC_FP32)
             hipLaunchKernelGGL((k_fill_image<float>), dim3((unsigned)ceil_div((int64_t)u->n, 256)), dim3(256), 0, ctx().stream, (const float *)a.u_val,
@@ -1856,26 +1809,23 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
         }
     }
     // BOOL: pack the values of the image the kernel indexes ([hot | u] or u) into bits
-    DevBuf<uint64_t> valbits(0);
+    DevPtr<uint64_t> valbits;
     // (u not full: presence and value share one word per 16 codes, one gather per entry instead of two -- every pull kernel
     //  but the chunk kernel of the long rows reads that form)
     const bool chunk_kernel = S->split.split_state == 1 && !((S->split.split_kind == 1 || S->split.split_kind == 2 || S->split.split_kind == 4) && S->split.long_nnz > 0);
     if (st == TC_BOOL && a.need_uval && !a.u_full && !chunk_kernel && !(ctx().debug_flags & 2048)) {
         const int64_t len = a.x_len;
-        dev_free(valbits.p);
-        valbits.p = (uint64_t *)dev_alloc((size_t)((len + 15) >> 4) * 4 + 8);
+        valbits.reset((uint64_t *)dev_alloc((size_t)((len + 15) >> 4) * 4 + 8));
         pack_bool_pv((const uint64_t *)a.u_bits, (const bool *)a.u_val, len, (uint32_t *)valbits.p);
         a.u_pv = (const uint32_t *)valbits.p;
         ctx().stats.kernel_launches += 1;
     } else if (st == TC_BOOL && a.need_uval) {
         const int64_t len = a.x_len;
-        dev_free(valbits.p);
-        valbits.p = (uint64_t *)dev_alloc(bits_words64((uint64_t)len) * 8);
-        DevBuf<uint64_t> allp(0);
+        valbits.reset((uint64_t *)dev_alloc(bits_words64((uint64_t)len) * 8));
+        DevPtr<uint64_t> allp;
         const uint64_t *pres = (const uint64_t *)a.u_bits;
         if (a.u_full) {  // no presence image in this case: every entry is present
-            dev_free(allp.p);
-            allp.p = (uint64_t *)dev_alloc(bits_words64((uint64_t)len) * 8);
+            allp.reset((uint64_t *)dev_alloc(bits_words64((uint64_t)len) * 8));
             GRB_HIP(hipMemsetAsync(allp.p, 0xff, bits_words64((uint64_t)len) * 8, ctx().stream));
             pres = allp.p;
         }
@@ -1924,16 +1874,8 @@ static void mxv_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
             a.w_new_bits = t->d_bits;
             a.fresh = 0;
             pull_dispatch(S, st, a);
-            DevBuf<char> tc((size_t)w->n * w->type->size);
-            cast_array(w->type->code, tc.p, st, t->d_val, (int64_t)w->n);
-            const int acc_op = accum ? canonical_op(w->type->code, accum->op) : -1;
-            GRB_DISPATCH_TYPE(w->type->code, TW, {
-                const int64_t nthreads = (int64_t)bits_words64(w->n) * 64;
-                hipLaunchKernelGGL((k_vec_write<TW>), dim3((unsigned)ceil_div(nthreads, 256)), dim3(256), 0, ctx().stream,
-                                   (int64_t)w->n, (const TW *)w->d_val, (const uint64_t *)w->d_bits, (TW *)w->d_val,
-                                   w->d_bits, (const TW *)tc.p, (const uint64_t *)t->d_bits, m_bits, mask ? 1 : 0,
-                                   f.comp ? 1 : 0, acc_op, f.replace ? 1 : 0, 0);
-            })
+            DevPtr<char> t_hold;
+            vector_finish(w, vector_values_as(t->d_val, st, w->type->code, (int64_t)w->n, t_hold), t->d_bits, m_bits, f, accum);
             ctx().stats.kernel_launches += 1;
         } catch (...) {
             vector_free(t);
@@ -1959,7 +1901,7 @@ static int widened_type_code(int st)
 // one atomic per entry of the frontier's rows (~20 G/s measured), pull streams all of S once (~270 G entries/s) -- the level
 // after a hub of a power-law graph has few vertices but a large share of the edges.
 static bool push_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum,
-                      const GB_Semiring_opaque *sr, GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, DescFlags f)
+                      const GB_Semiring_opaque *sr, GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, Desc f)
 {
     ctx().stats = GrX_Stats{};
     ctx().stats.method = 2;
@@ -1970,39 +1912,15 @@ static bool push_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bina
     int mult = canonical_op(st, sr->mult);
     if (flip) mult = flip_op(mult);  // the kernel evaluates mult(u_k, P_kj)
     // operands in the semiring's type
-    DevBuf<char> a_cast(0), u_cast(0);
-    const void *aval = P->d_val;
-    if (P->nvals && P->type->code != st) {
-        const int64_t nv = P->iso ? 1 : P->nvals;
-        dev_free(a_cast.p);
-        a_cast.p = (char *)dev_alloc(type_size(st) * (size_t)nv);
-        cast_array(st, a_cast.p, P->type->code, P->d_val, nv);
-        aval = a_cast.p;
-    }
-    const void *uval = u->d_val;
-    if (u->type->code != st) {
-        dev_free(u_cast.p);
-        u_cast.p = (char *)dev_alloc(type_size(st) * (size_t)u->n);
-        cast_array(st, u_cast.p, u->type->code, u->d_val, (int64_t)u->n);
-        uval = u_cast.p;
-    }
-    DevBuf<uint64_t> mbits_tmp(0);
-    const uint64_t *m_bits = nullptr;
-    if (mask) {
-        if (f.structure && mask->d_val && mask != w) m_bits = mask->d_bits;
-        else {
-            dev_free(mbits_tmp.p);
-            mbits_tmp.p = (uint64_t *)dev_alloc(bits_words64(mask->n) * 8);
-            vector_mask_bits(mask, f.structure, mbits_tmp.p);
-            m_bits = mbits_tmp.p;
-        }
-    }
+    DevPtr<char> a_hold, u_hold, t_hold;
+    DevPtr<uint64_t> m_hold;
+    const void *aval = values_as(P, st, a_hold);
+    const void *uval = vector_values_as(u->d_val, u->type->code, st, (int64_t)u->n, u_hold);
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
     // frontier list, its rows' lengths, prefix sums
     uint64_t *d_idx = nullptr;
     const int64_t fcount = vector_index_list(u, &d_idx);
-    DevBuf<uint64_t> idx_hold(0);
-    dev_free(idx_hold.p);
-    idx_hold.p = d_idx;
+    DevPtr<uint64_t> idx_hold(d_idx);
     int64_t work = 0;
     DevBuf<int64_t> pre(fcount + 1);
     if (fcount > 0 && P->nvals > 0) {
@@ -2034,17 +1952,7 @@ static bool push_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bina
     ctx().stats.flops = work;
     ctx().stats.kernel_launches += 4;
     // write rule, in place on w (w never aliases the dense accumulator); u == w is safe: u was read above
-    vector_ensure_storage(w);
-    DevBuf<char> tc((size_t)n_out * w->type->size);
-    cast_array(w->type->code, tc.p, wt, t_val.p, n_out);
-    const int acc_op = accum ? canonical_op(w->type->code, accum->op) : -1;
-    GRB_DISPATCH_TYPE(w->type->code, TW, {
-        const int64_t nthreads = (int64_t)bits_words64(w->n) * 64;
-        hipLaunchKernelGGL((k_vec_write<TW>), dim3((unsigned)ceil_div(nthreads, 256)), dim3(256), 0, ctx().stream, (int64_t)w->n,
-                           (const TW *)w->d_val, (const uint64_t *)w->d_bits, (TW *)w->d_val, w->d_bits, (const TW *)tc.p,
-                           (const uint64_t *)t_bits.p, m_bits, mask ? 1 : 0, f.comp ? 1 : 0, acc_op, f.replace ? 1 : 0, 0);
-    })
-    w->nvals = -1;
+    vector_finish(w, vector_values_as(t_val.p, wt, w->type->code, n_out, t_hold), t_bits.p, m_bits, f, accum);
     if (ctx().blocking) sync_stream();
     return true;
 }
@@ -2064,7 +1972,7 @@ static bool want_push(GB_Vector_opaque *u, GB_Matrix_opaque *P_or_null)
 // direction should run (u has too many entries, or its rows hold too many: decided from ONE host read), -1 when this path does not
 // apply (typecasts, a frontier beyond the queue) and the dense push path should be tried.
 static int push_thin(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                     GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, DescFlags f)
+                     GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, Desc f)
 {
     const int st = sr->type;
     const int monoid = canonical_op(st, sr->monoid);
@@ -2134,17 +2042,8 @@ static int push_thin(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
     if (ctx().push_mode == 1 && (fcount * 64 >= n_in || work * 128 > P->nvals)) return 0;
     if (fcount > a.f_cap || n_chunks > a.c_cap) return -1;
     if (ctx().push_mode == 1 && work * 8 > n_out) return -1;  // (the dense accumulator pays from here)
-    // ---- mask bits (a mask that aliases w is snapshotted) ----
-    DevBuf<uint64_t> mbits_tmp(0);
-    if (mask) {
-        if (f.structure && mask->d_val && mask != w) a.m_bits = mask->d_bits;
-        else {
-            dev_free(mbits_tmp.p);
-            mbits_tmp.p = (uint64_t *)dev_alloc(bits_words64(mask->n) * 8);
-            vector_mask_bits(mask, f.structure, mbits_tmp.p);
-            a.m_bits = mbits_tmp.p;
-        }
-    }
+    DevPtr<uint64_t> m_hold;
+    a.m_bits = vector_mask_words(mask, w, f.structure, m_hold);
     a.has_mask = mask ? 1 : 0;
     a.m_comp = f.comp ? 1 : 0;
     if (n_chunks == 0 && !w->d_val && w != u) {  // (a frontier of isolated vertices into a vector without storage: w stays as empty as it is)
@@ -2200,7 +2099,7 @@ static int push_thin(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
 
 // the push direction walks the rows of a matrix in natural order: its operands come back to it first
 static bool push_natural(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                         GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, DescFlags f)
+                         GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, Desc f)
 {
     vector_set_order(u, nullptr);
     vector_set_order(w, nullptr);
@@ -2210,7 +2109,7 @@ static bool push_natural(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_B
 
 // the push direction, thin path first; false: the pull direction runs
 static bool push_any(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                     GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, DescFlags f)
+                     GB_Matrix_opaque *P, GB_Vector_opaque *u, bool flip, Desc f)
 {
     if (!P || ctx().push_mode == 0 || u->nvals == 0 || P->nvals == 0 || !u->d_val) return false;
     const int thin = push_thin(w, mask, accum, sr, P, u, flip, f);
@@ -2223,7 +2122,7 @@ static bool push_any(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binar
 // matrix has (or now gets) one and the call can use it, otherwise on S with the operands in natural order.
 // (`u_token`: u stands for "present everywhere, values never read" -- the row reductions -- and has no storage to convert)
 static void mxv_any_order(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                          GB_Matrix_opaque *S, GB_Vector_opaque *u, bool flip, DescFlags f, bool u_token = false)
+                          GB_Matrix_opaque *S, GB_Vector_opaque *u, bool flip, Desc f, bool u_token = false)
 {
     const int64_t reorders0 = ctx().reorder_count;
     GB_Vector_opaque *vs[3] = {w, u_token ? nullptr : u, mask};
@@ -2299,12 +2198,12 @@ extern "C" GrB_Info GrB_mxv(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
     check_matrix(A, "A");
     check_vector_any(u, "u");
     if (!semiring) fail(GrB_NULL_POINTER, "semiring is NULL");
-    DescFlags f = flags_of(desc);
+    Desc f = desc_of(desc);
     // pull over S = A (or A' with T0); push needs the matrix whose ROWS are indexed like u: S' -- only when cached
     GB_Matrix_opaque *P = f.t0 ? A : A->tr;
     const bool dims_ok = (f.t0 ? A->nrows : A->ncols) == u->n && (f.t0 ? A->ncols : A->nrows) == w->n && (!mask || mask->n == w->n);
     if (op_is_positional(semiring->mult)) {  // (reads indices, not values: kernels of its own on the plain CSR arrays, grb_mxv_posn.hip)
-        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/false, mdesc_of(desc));
+        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/false, desc_of(desc));
     } else if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/true, f)) {
     } else {
         GB_Matrix_opaque *S = f.t0 ? matrix_transpose_cached(A) : A;
@@ -2323,13 +2222,13 @@ extern "C" GrB_Info GrB_vxm(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
     check_matrix(A, "A");
     check_vector_any(u, "u");
     if (!semiring) fail(GrB_NULL_POINTER, "semiring is NULL");
-    DescFlags f = flags_of(desc);
+    Desc f = desc_of(desc);
     // w' = u' A  <=>  w = A' u with the multiply operands swapped; desc T1 transposes A
     // push walks the rows of P = A (or A' with T1, when cached) selected by u; pull gathers over S = P'
     GB_Matrix_opaque *P = f.t1 ? A->tr : A;
     const bool dims_ok = (f.t1 ? A->ncols : A->nrows) == u->n && (f.t1 ? A->nrows : A->ncols) == w->n && (!mask || mask->n == w->n);
     if (op_is_positional(semiring->mult)) {
-        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/true, mdesc_of(desc));
+        mxv_positional(w, mask, accum, semiring, A, u, /*vxm=*/true, desc_of(desc));
     } else if (dims_ok && (!accum || (accum->type == w->type->code && !op_is_comparison(accum->op))) && !(!mask && f.comp) && w->n > 0 && push_any(w, mask, accum, semiring, P, u, /*flip=*/false, f)) {
     } else {
         GB_Matrix_opaque *S = f.t1 ? A : matrix_transpose_cached(A);
@@ -2495,7 +2394,7 @@ extern "C" GrB_Info GrB_Matrix_reduce_Monoid(GrB_Vector w, const GrB_Vector mask
     if (mask) check_vector_any(mask, "mask");
     check_matrix(A, "A");
     if (!monoid) fail(GrB_NULL_POINTER, "monoid is NULL");
-    DescFlags f = flags_of(desc);
+    Desc f = desc_of(desc);
     GB_Matrix_opaque *S = f.t0 ? matrix_transpose_cached(A) : A;
     f.t0 = false;
     const GB_Semiring_opaque sr = {monoid->op, OP_FIRST, monoid->type, "reduce"};

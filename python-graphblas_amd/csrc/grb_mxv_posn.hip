@@ -9,7 +9,7 @@
 // so every operator is one of OUTER (o), INNER (k), ZERO, plus an offset of 0 or 1 (pos_kind).  Monoids: MIN, MAX, ANY, PLUS.
 //
 // The kernels run on the plain CSR arrays (the pull layouts of grb_mxv.hip re-code the columns: the natural index is gone there), with
-// the vectors in natural order, build T = dense values + presence words in the semiring's type and end in vector_write_rule.
+// the vectors in natural order, build T = dense values + presence words in the semiring's type and end in vector_finish.
 //   pull  k_posn_pull over S (rows = outputs): a LANE GROUP of G = 4 / 8 / 16 / 64 lanes per row (G from the mean row length, the grid
 //         from the row count alone), G consecutive columns per step, the operand's presence bit, one __ballot.  Column lists are sorted:
 //         INNER under MIN / ANY ends at the first set lane, under MAX the row is walked from its end; OUTER / ZERO under MIN / MAX / ANY
@@ -172,7 +172,7 @@ static TS posn_identity(int mon)
 }
 
 void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, const GB_Semiring_opaque *sr,
-                    GB_Matrix_opaque *A, GB_Vector_opaque *u, bool vxm, MDesc f)
+                    GB_Matrix_opaque *A, GB_Vector_opaque *u, bool vxm, Desc f)
 {
     check_vector(w, "w");
     if (mask) check_vector(mask, "mask");
@@ -181,10 +181,7 @@ void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binary
     const bool tr = vxm ? f.t1 : f.t0;
     const uint64_t m_rows = tr ? A->ncols : A->nrows, m_cols = tr ? A->nrows : A->ncols;
     const uint64_t n_inner = vxm ? m_rows : m_cols, n_outer = vxm ? m_cols : m_rows;
-    if (n_inner != u->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: matrix inner dimension " + std::to_string(n_inner) + " does not match vector size " + std::to_string(u->n));
-    if (w->n != n_outer) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: output size " + std::to_string(w->n) + " does not match matrix dimension " + std::to_string(n_outer));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: mask size does not match output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "mxv/vxm: accum operator type must equal the output type");
+    check_mxv_sizes(n_inner, n_outer, w, mask, accum, u);
     ctx().stats = GrX_Stats{};
     ctx().stats.method = 25;
     ctx().stats.long_kernel = -1;
@@ -193,29 +190,16 @@ void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binary
     ctx().stats.out_nvals = -1;
     const int64_t n_out = (int64_t)w->n;
     if (n_out == 0) return;
-    if (!mask && f.comp) {  // complement of "no mask": nothing may be written
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    if (vector_writes_nothing(w, mask, f)) return;
     const int st = sr->type;
     if (!op_is_positional(sr->mult) || (st != TC_INT32 && st != TC_INT64)) fail(GrB_PANIC, "mxv/vxm: not a positional semiring (internal error)");
     const int mon = canonical_op(st, sr->monoid);
     if (mon != OP_MIN && mon != OP_MAX && mon != OP_ANY && mon != OP_PLUS)
         fail(GrB_NOT_IMPLEMENTED, std::string("mxv/vxm: the positional operator ") + pos_op_name(sr->mult) + " is implemented under the MIN, MAX, ANY and PLUS monoids only");
-    const int acc_op = accum ? canonical_op(w->type->code, accum->op) : -1;
+    if (accum) (void)canonical_op(w->type->code, accum->op);  // (an accumulator without a kernel is rejected before the short cut below)
     const int kind = pos_kind(sr->mult, vxm), off = (sr->mult - POS_FIRSTI) & 1;
-
-    // ---- mask bits (a mask that aliases w is snapshotted, as in mxv_core) ----
-    DevPtr<uint64_t> mbits_tmp;
-    const uint64_t *m_bits = nullptr;
-    if (mask) {
-        if (f.structure && mask->d_val && mask != w) m_bits = mask->d_bits;
-        else {
-            mbits_tmp.reset((uint64_t *)dev_alloc(bits_words64(mask->n) * 8));
-            vector_mask_bits(mask, f.structure, mbits_tmp.get());
-            m_bits = mbits_tmp.get();
-        }
-    }
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
 
     // ---- an operand without entries: T is empty, only the write rule remains ----
     const int64_t nv = vector_nvals(u);
@@ -228,9 +212,8 @@ void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binary
         }
         vector_ensure_storage(w);
         DevBuf<uint64_t> t_bits(bits_words64(w->n), true);
-        vector_write_rule(w, w->d_val, t_bits.p, m_bits, f.comp, acc_op, f.replace);
+        vector_finish(w, w->d_val, t_bits.p, m_bits, f, accum);
         ctx().stats.kernel_launches += 1;
-        w->nvals = -1;
         if (ctx().blocking) sync_stream();
         return;
     }
@@ -286,18 +269,10 @@ void mxv_positional(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Binary
     }
 
     // ---- T in w's type, then the write rule (in place on w; u == w is safe: u was read above, in stream order) ----
-    vector_ensure_storage(w);
-    DevPtr<char> tcast;
-    const void *tw = t_val.p;
-    if (w->type->code != st) {
-        tcast.reset((char *)dev_alloc(w->type->size * (size_t)n_out));
-        cast_array(w->type->code, tcast.get(), st, t_val.p, n_out);
-        tw = tcast.get();
-        ctx().stats.kernel_launches += 1;
-    }
-    vector_write_rule(w, tw, t_bits.p, m_bits, f.comp, acc_op, f.replace);
-    ctx().stats.kernel_launches += 1;
-    w->nvals = -1;
+    DevPtr<char> t_hold;
+    const void *tw = vector_values_as(t_val.p, st, w->type->code, n_out, t_hold);
+    vector_finish(w, tw, t_bits.p, m_bits, f, accum);
+    ctx().stats.kernel_launches += tw == t_val.p ? 1 : 2;  // (the write rule, and the cast in front of it)
     GRB_HIP(hipGetLastError());
     if (ctx().blocking) sync_stream();
 }

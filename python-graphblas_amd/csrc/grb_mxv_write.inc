@@ -117,9 +117,9 @@ __global__ void k_vec_write(int64_t n, const TW *w_old_val, const uint64_t *w_ol
     if (lane == 0 && g < nwords) w_new_bits[g] = nb;
 }
 
-// w<m_bits (^comp), replace> = accum(w, t), in place, t of w's type (shared with the element-wise operations of grb_vecops.hip)
-void vector_write_rule(GB_Vector_opaque *w, const void *t_val, const uint64_t *t_bits, const uint64_t *m_bits, bool comp, int accum,
-                       bool replace)
+// w<m_bits (^comp), replace> = accum(w, t), in place, t of w's type
+static void vector_write_rule(GB_Vector_opaque *w, const void *t_val, const uint64_t *t_bits, const uint64_t *m_bits, bool comp, int accum,
+                              bool replace)
 {
     GRB_DISPATCH_TYPE(w->type->code, TW, {
         const int64_t nthreads = (int64_t)bits_words64(w->n) * 64;
@@ -127,4 +127,12 @@ void vector_write_rule(GB_Vector_opaque *w, const void *t_val, const uint64_t *t
                            (const TW *)w->d_val, (const uint64_t *)w->d_bits, (TW *)w->d_val, w->d_bits, (const TW *)t_val, t_bits,
                            m_bits, m_bits ? 1 : 0, comp ? 1 : 0, accum, replace ? 1 : 0, 0);
     })
+}
+
+// the last step of every vector operation (DESIGN.md section 4.8)
+void vector_finish(GB_Vector_opaque *w, const void *t_val, const uint64_t *t_bits, const uint64_t *m_bits, Desc f, const GB_BinaryOp_opaque *accum)
+{
+    vector_ensure_storage(w);
+    vector_write_rule(w, t_val, t_bits, m_bits, f.comp, accum ? canonical_op(w->type->code, accum->op) : -1, f.replace);
+    w->nvals = -1;
 }

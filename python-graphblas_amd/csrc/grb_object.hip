@@ -461,7 +461,8 @@ GB_Vector_opaque *vector_cast_copy(GB_Vector_opaque *v, int type)
     return w;
 }
 
-void vector_mask_bits(GB_Vector_opaque *m, bool structure, uint64_t *out_bits)
+// out_bits = present(m) & (structure ? 1 : value != 0)
+static void vector_mask_bits(GB_Vector_opaque *m, bool structure, uint64_t *out_bits)
 {
     const size_t nw = bits_words64(m->n);
     if (!m->d_val) {
@@ -475,6 +476,52 @@ void vector_mask_bits(GB_Vector_opaque *m, bool structure, uint64_t *out_bits)
     GRB_DISPATCH_TYPE(m->type->code, T, {
         LAUNCH((k_mask_bits<T>), (int64_t)nw * 64, m->d_bits, (const T *)m->d_val, (int64_t)m->n, out_bits);
     })
+}
+
+// ---- the frame of the vector operations (vector_finish lives beside the write rule, grb_mxv_write.inc) ----
+static void check_vector_accum(const char *op, const GB_Vector_opaque *w, const GB_BinaryOp_opaque *accum)
+{
+    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op)))
+        fail(GrB_DOMAIN_MISMATCH, std::string(op) + ": accum operator type must equal the output type");
+}
+
+void check_vector_mask_accum(const char *op, const GB_Vector_opaque *w, const GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum)
+{
+    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, std::string(op) + ": mask size does not match the output size");
+    check_vector_accum(op, w, accum);
+}
+
+void check_mxv_sizes(uint64_t n_inner, uint64_t n_outer, const GB_Vector_opaque *w, const GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum,
+                     const GB_Vector_opaque *u)
+{
+    if (n_inner != u->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: matrix inner dimension " + std::to_string(n_inner) + " does not match vector size " + std::to_string(u->n));
+    if (w->n != n_outer) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: output size " + std::to_string(w->n) + " does not match matrix dimension " + std::to_string(n_outer));
+    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: mask size does not match output size");
+    check_vector_accum("mxv/vxm", w, accum);
+}
+
+bool vector_writes_nothing(GB_Vector_opaque *w, const GB_Vector_opaque *mask, Desc f)
+{
+    if (mask || !f.comp) return false;
+    if (f.replace) vector_release_storage(w);
+    return true;
+}
+
+const uint64_t *vector_mask_words(GB_Vector_opaque *mask, const GB_Vector_opaque *w, bool structure, DevPtr<uint64_t> &hold)
+{
+    if (!mask) return nullptr;
+    if (structure && mask->d_val && mask != w) return mask->d_bits;
+    hold.reset((uint64_t *)dev_alloc(bits_words64(mask->n) * 8));
+    vector_mask_bits(mask, structure, hold.get());
+    return hold.get();
+}
+
+const void *vector_values_as(const void *val, int from, int to, int64_t n, DevPtr<char> &hold)
+{
+    if (!val || from == to) return val;
+    hold.reset((char *)dev_alloc(type_size(to) * (size_t)n));
+    cast_array(to, hold.get(), from, val, n);
+    return hold.get();
 }
 
 // sort tuples by key, fold duplicates.  Returns number of unique keys; outputs are fresh device arrays.
@@ -1288,7 +1335,7 @@ extern "C" GrB_Info GrB_transpose(GrB_Matrix C, const GrB_Matrix Mask, const GrB
     check_matrix(C, "C");
     check_matrix(A, "A");
     if (Mask) check_matrix(Mask, "Mask");
-    const MDesc f = mdesc_of(desc);
+    const Desc f = desc_of(desc);
     GB_Matrix_opaque *S = f.t0 ? A : matrix_transpose_cached(A);  // transposing a transpose is a copy
     if (C->nrows != S->nrows || C->ncols != S->ncols) fail(GrB_DIMENSION_MISMATCH, "GrB_transpose: output shape mismatch");
     check_mask_accum("GrB_transpose", C, Mask, accum);

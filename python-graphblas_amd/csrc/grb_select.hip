@@ -274,7 +274,7 @@ static void matrix_select(GB_Matrix_opaque *C, GB_Matrix_opaque *Mask, const GB_
     check_matrix(A, "A");
     if (Mask) check_matrix(Mask, "Mask");
     check_select_op(op);
-    const MDesc f = mdesc_of(desc);  // (T1 is ignored: there is no second input)
+    const Desc f = desc_of(desc);  // (T1 is ignored: there is no second input)
     const uint64_t in_rows = f.t0 ? A->ncols : A->nrows, in_cols = f.t0 ? A->nrows : A->ncols;
     if (C->nrows != in_rows || C->ncols != in_cols)
         fail(GrB_DIMENSION_MISMATCH, "GrB_select: output is " + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + ", the input " +
@@ -304,14 +304,10 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
         check_vector(u, "u");
         if (mask) check_vector(mask, "mask");
     }
-    const bool replace = desc && desc->replace, comp = desc && desc->comp, structure = desc && desc->structure;
+    const Desc f = desc_of(desc);
     if (w->n != u->n) fail(GrB_DIMENSION_MISMATCH, "GrB_select: output size " + std::to_string(w->n) + " does not match the input size " + std::to_string(u->n));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "GrB_select: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "GrB_select: accum operator type must equal the output type");
-    if (!mask && comp) {
-        if (replace) vector_release_storage(w);
-        return;
-    }
+    check_vector_mask_accum("GrB_select", w, mask, accum);
+    if (vector_writes_nothing(w, mask, f)) return;
     ctx().stats = GrX_Stats{};
     if (w->n == 0) return;
     if (sel_is_value(code)) {
@@ -322,7 +318,8 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
     const size_t nwords = bits_words64((uint64_t)n);
     const int64_t threads = (int64_t)nwords * 64;
     DevBuf<uint64_t> t_bits(nwords);
-    DevPtr<char> xcast, tcast;
+    DevPtr<char> x_hold, t_hold;
+    DevPtr<uint64_t> m_hold;
     if (!u->d_val) {
         GRB_HIP(hipMemsetAsync(t_bits.p, 0, nwords * 8, ctx().stream));
     } else if (!sel_is_value(code)) {
@@ -342,27 +339,22 @@ static void vector_select(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_
         ctx().stats.kernel_launches += 1;
     } else {
         const int ot = op->type;
-        const void *xs = u->d_val;
-        if (ot != u->type->code) {
-            xcast.p = (char *)dev_alloc(type_size(ot) * (size_t)n);
-            cast_array(ot, xcast.p, u->type->code, u->d_val, n);
-            xs = xcast.p;
-        }
+        const void *xs = vector_values_as(u->d_val, u->type->code, ot, n, x_hold);
         GRB_DISPATCH_TYPE(ot, TO, { launch_vselect_value<TO>(code, grid1d(threads), n, xs, (const uint64_t *)u->d_bits, thunk_as<TO>(th), t_bits.p); })
         ctx().stats.kernel_launches += 1;
     }
     // t's values in w's type (a buffer of its own when w is u: the write rule works in place)
-    DevBuf<uint64_t> mbits(mask ? nwords : 1);
-    if (mask) vector_mask_bits(mask, structure, mbits.p);
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
     vector_ensure_storage(w);
-    const void *tw = u->d_val ? u->d_val : w->d_val;
-    if (u->d_val && (w == u || w->type->code != u->type->code)) {
-        tcast.p = (char *)dev_alloc(w->type->size * (size_t)n);
-        cast_array(w->type->code, tcast.p, u->type->code, u->d_val, n);
-        tw = tcast.p;
+    const void *tw = w->d_val;  // (u without entries: t_bits is zero, any array of w's type will do)
+    if (w == u) {
+        t_hold.reset((char *)dev_alloc(w->type->size * (size_t)n));
+        d2d(t_hold.get(), u->d_val, w->type->size * (size_t)n);
+        tw = t_hold.get();
+    } else if (u->d_val) {
+        tw = vector_values_as(u->d_val, u->type->code, w->type->code, n, t_hold);
     }
-    vector_write_rule(w, tw, t_bits.p, mask ? mbits.p : nullptr, comp, accum ? canonical_op(w->type->code, accum->op) : -1, replace);
-    w->nvals = -1;
+    vector_finish(w, tw, t_bits.p, m_bits, f, accum);
     GRB_HIP(hipGetLastError());
     if (ctx().blocking) sync_stream();
 }

@@ -408,7 +408,7 @@ static void matrix_sort(GB_Matrix_opaque *C, GB_Matrix_opaque *P, const GB_Binar
         if (P) TP = sort_transposed(TP);
     }
     // both outputs are built before either is written: C, P and A may alias one another
-    const MDesc plain;
+    const Desc plain;
     if (C) matrix_finish(C, nullptr, nullptr, std::move(TC), plain, C == A);
     if (P) matrix_finish(P, nullptr, nullptr, std::move(TP), plain, P == A);
     ctx().stats.out_nvals = C ? C->nvals : P->nvals;
@@ -548,7 +548,7 @@ static void matrix_reverse_rows(GB_Matrix_opaque *C, GB_Matrix_opaque *A)
         }
         matrix_adopt(T.get(), Tp.release(), Tj.release(), raw.release(), A->type->code, nnz, A->iso);
     }
-    matrix_finish(C, nullptr, nullptr, std::move(T), MDesc{}, C == A);
+    matrix_finish(C, nullptr, nullptr, std::move(T), Desc{}, C == A);
     ctx().stats.out_nvals = C->nvals;
     GRB_HIP(hipGetLastError());
     if (ctx().blocking) sync_stream();

@@ -148,16 +148,6 @@ __global__ void k_ewise(int64_t n, const T *u_val, const uint64_t *u_bits, const
     if (lane == 0 && g < ((n + 63) >> 6)) t_bits[g] = b;
 }
 
-struct VDesc {
-    bool replace = false, comp = false, structure = false;
-};
-static VDesc vflags(const GB_Descriptor_opaque *d)
-{
-    VDesc f;
-    if (d) { f.replace = d->replace; f.comp = d->comp; f.structure = d->structure; }
-    return f;
-}
-
 template <typename T>
 static void set_element(GB_Vector_opaque *w, T x, uint64_t i)
 {
@@ -193,29 +183,25 @@ static GrB_Info extract_element(T *x, GB_Vector_opaque *u, uint64_t i)
 template <typename T>
 static void assign_all(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, T x, const GB_Descriptor_opaque *desc)
 {
-    const VDesc f = vflags(desc);
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "assign: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "assign: accum operator type must equal the output type");
-    if (!mask && f.comp) {  // complement of "no mask": nothing may be written
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    const Desc f = desc_of(desc);
+    check_vector_mask_accum("assign", w, mask, accum);
+    if (vector_writes_nothing(w, mask, f)) return;
     if (w->n == 0) return;
     {   // element-wise: any vertex order will do, as long as it is the same for w and the mask
         GB_Vector_opaque *vs[2] = {w, mask};
         (void)vectors_common_order(vs, 2);
     }
     vector_ensure_storage(w);
-    DevBuf<uint64_t> mbits(mask ? bits_words64(w->n) : 1);
-    if (mask) vector_mask_bits(mask, f.structure, mbits.p);  // (a snapshot: the mask may be w itself)
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
     GRB_DISPATCH_TYPE(w->type->code, TW, {
         const int64_t threads = (int64_t)bits_words64(w->n) * 64;
         hipLaunchKernelGGL((k_assign_all<TW>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx().stream, (int64_t)w->n,
-                           (TW *)w->d_val, w->d_bits, (const uint64_t *)mbits.p, mask ? 1 : 0, f.comp ? 1 : 0,
+                           (TW *)w->d_val, w->d_bits, m_bits, mask ? 1 : 0, f.comp ? 1 : 0,
                            accum ? canonical_op(w->type->code, accum->op) : -1, f.replace ? 1 : 0, cast_value<TW, T>(x));
     })
     w->nvals = !mask ? (int64_t)w->n : -1;
-    if (ctx().blocking) sync_stream();  // (mbits goes back to the stream-ordered block cache: no wait needed)
+    if (ctx().blocking) sync_stream();  // (a snapshot of the mask goes back to the stream-ordered block cache: no wait needed)
 }
 
 template <typename T>
@@ -231,14 +217,8 @@ static void reduce_to(T *val, const GB_BinaryOp_opaque *accum, const GB_Monoid_o
         W h = monoid_identity<TM, W>(op);
         if (u->d_val && u->n > 0) {
             // values in the monoid's type
-            DevBuf<char> cast_buf(0);
-            const void *src = u->d_val;
-            if (u->type->code != mt) {
-                dev_free(cast_buf.p);
-                cast_buf.p = (char *)dev_alloc(sizeof(TM) * (size_t)u->n);
-                cast_array(mt, cast_buf.p, u->type->code, u->d_val, (int64_t)u->n);
-                src = cast_buf.p;
-            }
+            DevPtr<char> u_hold;
+            const void *src = vector_values_as(u->d_val, u->type->code, mt, (int64_t)u->n, u_hold);
             DevBuf<W> out(2);
             // (the slot starts at the accumulator seed, not the identity: a sum of -0.0 stays -0.0, a min / max over NaN alone is NaN;
             //  out[1] says whether any value came in -- an empty vector keeps the identity)
@@ -329,15 +309,11 @@ static void ewise_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bin
                        GB_Vector_opaque *u, GB_Vector_opaque *v, const GB_Descriptor_opaque *desc, bool is_add, const Thunk *alpha = nullptr,
                        const Thunk *beta = nullptr)
 {
-    const VDesc f = vflags(desc);
+    const Desc f = desc_of(desc);
     if (u->n != v->n) fail(GrB_DIMENSION_MISMATCH, "eWise: input sizes " + std::to_string(u->n) + " and " + std::to_string(v->n) + " differ");
     if (w->n != u->n) fail(GrB_DIMENSION_MISMATCH, "eWise: output size does not match the inputs");
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "eWise: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "eWise: accum operator type must equal the output type");
-    if (!mask && f.comp) {
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    check_vector_mask_accum("eWise", w, mask, accum);
+    if (vector_writes_nothing(w, mask, f)) return;
     if (w->n == 0) return;
     {   // element-wise: any vertex order will do, as long as all four vectors are in it
         GB_Vector_opaque *vs[4] = {w, u, v, mask};
@@ -349,20 +325,8 @@ static void ewise_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bin
     const int tt = cmp ? (int)TC_BOOL : ot;  // type of the element-wise result
     const size_t ob = type_size(ot);
     // operands in the operator's type
-    DevBuf<char> u_cast(0), v_cast(0);
-    const void *uv = u->d_val, *vv = v->d_val;
-    if (u->d_val && u->type->code != ot) {
-        dev_free(u_cast.p);
-        u_cast.p = (char *)dev_alloc(ob * (size_t)n);
-        cast_array(ot, u_cast.p, u->type->code, u->d_val, n);
-        uv = u_cast.p;
-    }
-    if (v->d_val && v->type->code != ot) {
-        dev_free(v_cast.p);
-        v_cast.p = (char *)dev_alloc(ob * (size_t)n);
-        cast_array(ot, v_cast.p, v->type->code, v->d_val, n);
-        vv = v_cast.p;
-    }
+    DevPtr<char> u_hold, v_hold, t_hold;
+    const void *uv = vector_values_as(u->d_val, u->type->code, ot, n, u_hold), *vv = vector_values_as(v->d_val, v->type->code, ot, n, v_hold);
     DevBuf<char> t_val(std::max(ob, type_size(tt)) * (size_t)n);
     DevBuf<uint64_t> t_bits(bits_words64((uint64_t)n));
     const int64_t threads = (int64_t)bits_words64((uint64_t)n) * 64;
@@ -387,19 +351,9 @@ static void ewise_core(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_Bin
                                (const uint64_t *)(v->d_val ? v->d_bits : nullptr), op, is_add ? 1 : 0, (T *)t_val.p, t_bits.p);
     })
     // the write rule in w's type (w may be u or v: t is a separate buffer, the rule is element-wise)
-    DevBuf<uint64_t> mbits(mask ? bits_words64(w->n) : 1);
-    if (mask) vector_mask_bits(mask, f.structure, mbits.p);
-    vector_ensure_storage(w);
-    DevBuf<char> tc(0);
-    const void *tw = t_val.p;
-    if (w->type->code != tt) {
-        dev_free(tc.p);
-        tc.p = (char *)dev_alloc(w->type->size * (size_t)n);
-        cast_array(w->type->code, tc.p, tt, t_val.p, n);
-        tw = tc.p;
-    }
-    vector_write_rule(w, tw, t_bits.p, mask ? mbits.p : nullptr, f.comp, accum ? canonical_op(w->type->code, accum->op) : -1, f.replace);
-    w->nvals = -1;
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
+    vector_finish(w, vector_values_as(t_val.p, tt, w->type->code, n, t_hold), t_bits.p, m_bits, f, accum);
     if (ctx().blocking) sync_stream();
 }
 
@@ -465,60 +419,45 @@ static void check_oob(int *d_flag, const char *what)
 static void assign_indexed(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, GB_Vector_opaque *u,
                            const void *scalar_w, const uint64_t *indices, uint64_t ni, const GB_Descriptor_opaque *desc)
 {
-    const VDesc f = vflags(desc);
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "assign: mask size does not match the output size");
+    const Desc f = desc_of(desc);
     if (u && u->n != ni) fail(GrB_DIMENSION_MISMATCH, "assign: the input has " + std::to_string(u->n) + " elements, the index list " + std::to_string(ni));
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "assign: accum operator type must equal the output type");
+    check_vector_mask_accum("assign", w, mask, accum);
     if (!indices) fail(GrB_NULL_POINTER, "assign: index list is NULL");
-    if (!mask && f.comp) {
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    if (vector_writes_nothing(w, mask, f)) return;
     if (w->n == 0) return;
     vector_ensure_storage(w);
     const int wt = w->type->code;
+    const size_t w_bytes = w->type->size * (size_t)w->n, w_words = bits_words64(w->n) * 8;
     DevBuf<uint64_t> d_idx(ni);
     if (ni) h2d(d_idx.p, indices, sizeof(uint64_t) * (size_t)ni);
     // u in w's type
-    DevBuf<char> u_cast(0);
+    DevPtr<char> u_hold, u_snap, zv;
+    DevPtr<uint64_t> ub_snap, zb, m_hold;
     const void *uval = nullptr;
     const uint64_t *ubits = nullptr;
     if (u) {
         vector_ensure_storage(u);
-        uval = u->d_val;
+        uval = vector_values_as(u->d_val, u->type->code, wt, (int64_t)u->n, u_hold);
         ubits = u->d_bits;
-        if (u->type->code != wt) {
-            dev_free(u_cast.p);
-            u_cast.p = (char *)dev_alloc(w->type->size * (size_t)std::max<uint64_t>(u->n, 1));
-            cast_array(wt, u_cast.p, u->type->code, u->d_val, (int64_t)u->n);
-            uval = u_cast.p;
-        }
     }
     // Z: w itself when nothing masks the write, else a copy
     void *z_val = w->d_val;
     uint64_t *z_bits = w->d_bits;
-    DevBuf<char> zv(0);
-    DevBuf<uint64_t> zb(0);
-    const bool in_place = !mask && !(u == w);
-    DevBuf<char> u_snap(0);
-    DevBuf<uint64_t> ub_snap(0);
     if (u == w) {  // (aliased input: read a snapshot)
-        dev_free(u_snap.p); dev_free(ub_snap.p);
-        u_snap.p = (char *)dev_alloc(w->type->size * (size_t)w->n);
-        ub_snap.p = (uint64_t *)dev_alloc(bits_words64(w->n) * 8);
-        d2d(u_snap.p, w->d_val, w->type->size * (size_t)w->n);
-        d2d(ub_snap.p, w->d_bits, bits_words64(w->n) * 8);
-        uval = u_snap.p;
-        ubits = ub_snap.p;
+        u_snap.reset((char *)dev_alloc(w_bytes));
+        ub_snap.reset((uint64_t *)dev_alloc(w_words));
+        d2d(u_snap.get(), w->d_val, w_bytes);
+        d2d(ub_snap.get(), w->d_bits, w_words);
+        uval = u_snap.get();
+        ubits = ub_snap.get();
     }
-    if (!in_place && mask) {
-        dev_free(zv.p); dev_free(zb.p);
-        zv.p = (char *)dev_alloc(w->type->size * (size_t)w->n);
-        zb.p = (uint64_t *)dev_alloc(bits_words64(w->n) * 8);
-        d2d(zv.p, w->d_val, w->type->size * (size_t)w->n);
-        d2d(zb.p, w->d_bits, bits_words64(w->n) * 8);
-        z_val = zv.p;
-        z_bits = zb.p;
+    if (mask) {
+        zv.reset((char *)dev_alloc(w_bytes));
+        zb.reset((uint64_t *)dev_alloc(w_words));
+        d2d(zv.get(), w->d_val, w_bytes);
+        d2d(zb.get(), w->d_bits, w_words);
+        z_val = zv.get();
+        z_bits = zb.get();
     }
     DevBuf<int> oob(1, true);
     if (ni) {
@@ -531,11 +470,8 @@ static void assign_indexed(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB
         })
     }
     check_oob(oob.p, "assign");
-    if (mask) {
-        DevBuf<uint64_t> mbits(bits_words64(w->n));
-        vector_mask_bits(mask, f.structure, mbits.p);
-        vector_write_rule(w, z_val, z_bits, mbits.p, f.comp, -1, f.replace);
-    }
+    // (the accumulator went into Z: the write rule only masks)
+    if (mask) vector_finish(w, z_val, z_bits, vector_mask_words(mask, w, f.structure, m_hold), f, nullptr);
     w->nvals = -1;
     sync_stream();  // (the index list was a host array borrowed for the call; temporaries go back to the block cache)
 }
@@ -543,15 +479,11 @@ static void assign_indexed(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB
 static void extract_indexed(GB_Vector_opaque *w, GB_Vector_opaque *mask, const GB_BinaryOp_opaque *accum, GB_Vector_opaque *u,
                             const uint64_t *indices, uint64_t ni, const GB_Descriptor_opaque *desc)
 {
-    const VDesc f = vflags(desc);
+    const Desc f = desc_of(desc);
     if (w->n != ni) fail(GrB_DIMENSION_MISMATCH, "extract: the output has " + std::to_string(w->n) + " elements, the index list " + std::to_string(ni));
-    if (mask && mask->n != w->n) fail(GrB_DIMENSION_MISMATCH, "extract: mask size does not match the output size");
-    if (accum && (accum->type != w->type->code || op_is_comparison(accum->op))) fail(GrB_DOMAIN_MISMATCH, "extract: accum operator type must equal the output type");
+    check_vector_mask_accum("extract", w, mask, accum);
     if (!indices) fail(GrB_NULL_POINTER, "extract: index list is NULL");
-    if (!mask && f.comp) {
-        if (f.replace) vector_release_storage(w);
-        return;
-    }
+    if (vector_writes_nothing(w, mask, f)) return;
     if (ni == 0) return;
     DevBuf<uint64_t> d_idx(ni);
     h2d(d_idx.p, indices, sizeof(uint64_t) * (size_t)ni);
@@ -565,19 +497,10 @@ static void extract_indexed(GB_Vector_opaque *w, GB_Vector_opaque *mask, const G
                            (const uint64_t *)(u->d_val ? u->d_bits : nullptr), oob.p);
     })
     check_oob(oob.p, "extract");
-    vector_ensure_storage(w);
-    DevBuf<char> tc(0);
-    const void *tw = t_val.p;
-    if (w->type->code != ut) {
-        dev_free(tc.p);
-        tc.p = (char *)dev_alloc(w->type->size * (size_t)ni);
-        cast_array(w->type->code, tc.p, ut, t_val.p, (int64_t)ni);
-        tw = tc.p;
-    }
-    DevBuf<uint64_t> mbits(mask ? bits_words64(w->n) : 1);
-    if (mask) vector_mask_bits(mask, f.structure, mbits.p);
-    vector_write_rule(w, tw, t_bits.p, mask ? mbits.p : nullptr, f.comp, accum ? canonical_op(w->type->code, accum->op) : -1, f.replace);
-    w->nvals = -1;
+    DevPtr<char> t_hold;
+    DevPtr<uint64_t> m_hold;
+    const uint64_t *m_bits = vector_mask_words(mask, w, f.structure, m_hold);
+    vector_finish(w, vector_values_as(t_val.p, ut, w->type->code, (int64_t)ni, t_hold), t_bits.p, m_bits, f, accum);
     sync_stream();
 }
 
